@@ -89,6 +89,28 @@ def cpu_baseline(sd, cfg_kw, inp, budget_s):
                        % (n, el, best, {k: round(v, 1) for k, v in sweep.items()}))
 
 
+DUMP_LIMIT = 64 << 20       # --dump-outputs: bytes in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT, seed=0):
+    """Write `arrays` (name -> [rows, ...] array of one step, same row count) as out_dir/<name>.npy in float32 (float64 stays float64).  When
+    the whole would pass `limit` bytes, a fixed seeded sample of rows is written instead, and its sorted row indices as out_dir/rows.npy."""
+    arrays = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = {v.shape[0] for v in arrays.values()}
+    assert len(n) == 1, "dump_outputs: arrays of different row counts"
+    n = n.pop()
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    room = limit - 256 * (len(arrays) + 1)
+    if n * row_bytes > room:
+        rows = np.sort(np.random.default_rng(seed).choice(n, room // (row_bytes + 8), replace=False))
+        arrays = dict({k: v[rows] for k, v in arrays.items()}, rows=rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrays)
+
+
 def split_steps(k, F):
     """k steps as ceil(k/F) launches of near-equal size (20 steps, F = 8 -> 7 + 7 + 6, never a half-empty 8 + 8 + 4)."""
     if k <= 0:
@@ -547,7 +569,12 @@ def main():
     ap.add_argument("--no-variants", action="store_true", help="skip the secondary-precision / full-step / end-to-end measurements")
     ap.add_argument("--e2e-frames", type=int, default=20, help="frames of the simulated-tracker end-to-end leg (0 = skip)")
     ap.add_argument("--split-steps", type=int, default=20, help="steps of the cfg5 split-tracks leg (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the LAST timed step computed (logits, probs, argmax of its --lost tracks) as DIR/<name>.npy in float32; "
+                         "the inputs depend on the arguments only, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     gpus_given = args.gpus is not None
     if not gpus_given:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -619,6 +646,11 @@ def main():
     k_avg, k_n = C.c_double(0), C.c_int64(0)
     ctx.lib.busca_timing_read(ctx.h, C.byref(k_avg), C.byref(k_n), 1)
     ctx.lib.busca_timing_enable(ctx.h, 0)
+    if args.dump_outputs and rank == 0:
+        # read back before the latency / variant legs reuse the output buffers: the last timed step = the last B tracks of the last launch
+        last = split_steps(args.steps, F)[-1]
+        rows = slice((last - 1) * B, last * B)
+        dump_outputs(args.dump_outputs, {"logits": run.logits[rows], "probs": run.probs[rows], "argmax": run.amax[rows]})
     my_elapsed = elapsed
     ev_ms = ev0.elapsed_time(ev1)
     elapsed = sharding.max_over_ranks(elapsed, dist, red_dev)

@@ -24,6 +24,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 REF = "/root/reference"
 OUT = os.path.join(ROOT, "tests", "golden")
+# torch CPU threads the fixtures were recorded with: oneDNN / MKL split float32 reductions by thread count, so the
+# oracle tests reproduce the reference's float32 bits only with the same count (tests/test_oracle_golden.py)
+GOLDEN_THREADS = 8
 sys.path.insert(0, ROOT)
 
 from busca_amd import synth  # noqa: E402
@@ -632,6 +635,7 @@ def make_track(ref):
 
 def main():
     which = set(sys.argv[1:]) or {"dt", "enc", "geom", "assoc", "reid", "track"}
+    torch.set_num_threads(GOLDEN_THREADS)
     ref = import_reference()
     if "dt" in which:
         make_dt(ref)

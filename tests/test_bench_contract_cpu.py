@@ -64,3 +64,23 @@ def test_emit_writes_the_detail_file_and_one_line(bench, tmp_path, capsys):
     assert out.count("\n") == 1 and json.loads(out)["detail"] == "detail.json"
     full = json.load(open(str(tmp_path / "detail.json")))
     assert full["assoc_e2e"]["blob"] == "b" * 5000 and full["value"] == res["value"]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(bench, tmp_path):
+    """--dump-outputs: one step's arrays as <name>.npy in float32 / float64; past the byte limit a fixed seeded sample of rows and its indices."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    arrays = {"logits": rng.standard_normal((32, 18)).astype(np.float32), "argmax": rng.integers(0, 18, 32).astype(np.int32),
+              "boxes": rng.standard_normal((32, 4))}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == ["argmax", "boxes", "logits"]
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in arrays}
+    assert got["logits"].dtype == np.float32 and got["argmax"].dtype == np.float32 and got["boxes"].dtype == np.float64
+    assert all(np.array_equal(got[k], arrays[k]) for k in arrays)
+    limit = 4096
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), arrays, limit=limit) == ["argmax", "boxes", "logits", "rows"]
+    files = sorted((tmp_path / "s1").iterdir())
+    assert sum(f.stat().st_size for f in files) <= limit
+    rows = np.load(str(tmp_path / "s1" / "rows.npy"))
+    assert 0 < len(rows) < 32 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(str(tmp_path / "s2" / "rows.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "logits.npy")), arrays["logits"][rows.astype(np.int64)])

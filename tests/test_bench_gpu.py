@@ -64,13 +64,25 @@ def test_bench_exact_driver_command(tmp_path):
 
 def test_bench_contract_single_gpu(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-variants",
-                        "--cpu-seconds", "2", "--latency-samples", "50", "--detail", str(tmp_path / "d.json")], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--cpu-seconds", "2", "--latency-samples", "50", "--detail", str(tmp_path / "d.json"), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     rf = _check_contract(d, 20, 5)
     assert rf["steps_per_launch"] == 20 and d["config"]["launches_in_timed_region"] == 1     # K steps = ONE launch (whole rounds + the token-split tail)
     full = json.load(open(str(tmp_path / "d.json")))["roofline"]
     assert rf["traffic"] is not None or "no PMC run" in full["traffic_note"]          # never a neighbouring shape's number
+    # --dump-outputs: the last timed step = the last 32 of the launch's 640 tracks, against the oracle on the same seeded inputs
+    import numpy as np
+    from busca_amd import synth
+    from oracle import dt as odt
+    assert sorted(os.listdir(str(tmp_path / "out"))) == ["argmax.npy", "logits.npy", "probs.npy"]
+    got = {k: np.load(str(tmp_path / "out" / (k + ".npy"))) for k in ("logits", "probs", "argmax")}
+    assert all(v.dtype == np.float32 for v in got.values()) and got["logits"].shape == got["probs"].shape == (32, 18) and got["argmax"].shape == (32,)
+    inp = {k: v[19 * 32:] for k, v in synth.dt_inputs(7, 20 * 32, 11, 16).items()}
+    ref = odt.dt_forward(synth.dt_state_dict(7, d=256, ff=512), odt.DTConfig(d=256, ff=512), **inp, return_all=True)
+    assert np.abs(got["logits"] - ref["logits"].numpy()).max() <= 2e-4 and np.abs(got["probs"] - ref["probs"].numpy()).max() <= 2e-5   # test_dt_gpu.TOL["f32"]
+    assert np.array_equal(got["argmax"], got["probs"].argmax(-1))
 
 
 def _check_two_ranks(d, full):

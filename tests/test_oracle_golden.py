@@ -5,11 +5,25 @@ import os
 
 import numpy as np
 import pytest
+import torch
 
 from busca_amd import synth
 from oracle import dt as odt
 
 DT_SETS = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "dt_*.npz")))
+
+
+@pytest.fixture(autouse=True)
+def golden_threads():
+    """The oracle's float32 convolutions and GEMMs on the thread count the fixtures were recorded with: their reduction order depends on it,
+    and the tolerances below hold the oracle to the reference's own bits (on a 128-thread host the ReID features otherwise move by 5e-6)."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+    from make_golden import GOLDEN_THREADS
+    n = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(n)
 
 
 @pytest.mark.parametrize("path", DT_SETS, ids=[os.path.basename(p)[:-4] for p in DT_SETS])
