@@ -16,6 +16,29 @@ int ensure_lds(busca_ctx* c, const void* kern, size_t bytes) {
     return BUSCA_OK;
 }
 
+// The options of a context, one entry each: the environment variable read at busca_ctx_create (NULL: none), the busca_set_option / busca_get_option
+// name (NULL: environment only), the field, and how a value is taken.  ("dt_status", "reid_status" and the "reid_*" schedule knobs are not fields of
+// BuscaOptions: explicit lines below, and REID_KNOBS in reid_state.hip.inc.)
+enum { OPT_INT /* the integer as it is */, OPT_FLAG /* set: value != 0 */, OPT_PRESENT /* environment: 1 when the variable is set at all; option: the integer */, OPT_READONLY /* get only */ };
+struct BuscaOptionDesc { const char* env; const char* opt; int BuscaOptions::*field; int kind; };
+static const BuscaOptionDesc BUSCA_OPTIONS[] = {
+    {"BUSCA_DT_NTRK", "dt_ntrk", &BuscaOptions::dt_ntrk, OPT_INT}, {"BUSCA_DT_TILED", "dt_tiled", &BuscaOptions::dt_tiled, OPT_PRESENT},
+    {"BUSCA_DT_SPLIT", "dt_split", &BuscaOptions::dt_split, OPT_INT}, {"BUSCA_DT_PROF", nullptr, &BuscaOptions::dt_prof, OPT_INT},
+    {"BUSCA_DTL_RT", nullptr, &BuscaOptions::dtl_rt, OPT_INT}, {"BUSCA_DTL_RT_MASK", nullptr, &BuscaOptions::dtl_rt_mask, OPT_INT},
+    {"BUSCA_DTL_FFN", nullptr, &BuscaOptions::dtl_ffn, OPT_INT}, {"BUSCA_DTL_ATTN", nullptr, &BuscaOptions::dtl_attn, OPT_INT},
+    {"BUSCA_CROP_BAND", "crop_band", &BuscaOptions::crop_band, OPT_INT}, {nullptr, "dt_exact_f32", &BuscaOptions::dt_exact_f32, OPT_FLAG},
+    {nullptr, "last_dt_grid", &BuscaOptions::last_dt_grid, OPT_READONLY}, {nullptr, "last_dt_ntrk", &BuscaOptions::last_dt_ntrk, OPT_READONLY},
+    {nullptr, "last_dt_split", &BuscaOptions::last_dt_split, OPT_READONLY},
+};
+static const BuscaOptionDesc* option_by_name(const char* name) {
+    for (const BuscaOptionDesc& e : BUSCA_OPTIONS) if (e.opt && !strcmp(e.opt, name)) return &e;
+    return nullptr;
+}
+static void options_from_env(BuscaOptions& o) {
+    for (const BuscaOptionDesc& e : BUSCA_OPTIONS)
+        if (const char* t = e.env ? getenv(e.env) : nullptr) o.*e.field = e.kind == OPT_PRESENT ? 1 : atoi(t);
+}
+
 extern "C" int busca_version(void) { return 2000; }
 
 static std::string g_create_err;   // busca_last_error(NULL) reports why busca_ctx_create failed
@@ -34,7 +57,7 @@ extern "C" int busca_ctx_create(int device, busca_ctx** out) {
     if (e != hipSuccess) { g_create_err = std::string("hipSetDevice: ") + hipGetErrorString(e); return BUSCA_EHIP; }
     busca_ctx* c = new busca_ctx();
     c->device = device;
-    c->opt.from_env();
+    options_from_env(c->opt);
     c->reid = reid_state_new();
     *out = c;
     return BUSCA_OK;
@@ -47,34 +70,22 @@ extern "C" const char* busca_build_info(void) { return "libbusca_hip gfx950 flag
 
 extern "C" int busca_set_option(busca_ctx* c, const char* name, int32_t value) {
     if (!c || !name) return BUSCA_EINVAL;
-    BuscaOptions& o = c->opt;
-    const std::string n(name);
-    if (n.rfind("reid_", 0) == 0) return reid_set_option(c, name, value);
-    if (n == "dt_ntrk") o.dt_ntrk = value;
-    else if (n == "dt_split") o.dt_split = value;
-    else if (n == "dt_tiled") o.dt_tiled = value;
-    else if (n == "crop_band") o.crop_band = value;
-    else if (n == "dt_exact_f32") o.dt_exact_f32 = value != 0;
-    else if (n == "dt_status") { if (c->dt.xerr) *c->dt.xerr = value; }      // 0 = the caller has read the status of its synchronised forward and dealt with it
-    else return fail(c, BUSCA_EINVAL, "busca_set_option: unknown option '%s'", name);
+    if (!strncmp(name, "reid_", 5)) return reid_set_option(c, name, value);
+    if (!strcmp(name, "dt_status")) { if (c->dt.xerr) *c->dt.xerr = value; return BUSCA_OK; }      // 0 = the caller has read the status of its synchronised forward and dealt with it
+    const BuscaOptionDesc* e = option_by_name(name);
+    if (!e || e->kind == OPT_READONLY) return fail(c, BUSCA_EINVAL, "busca_set_option: unknown option '%s'", name);
+    c->opt.*e->field = e->kind == OPT_FLAG ? value != 0 : value;
     return BUSCA_OK;
 }
 extern "C" int busca_get_option(busca_ctx* c, const char* name, int32_t* value) {
     if (!c || !name || !value) return BUSCA_EINVAL;
-    const BuscaOptions& o = c->opt;
-    const std::string n(name);
-    if (n.rfind("reid_", 0) == 0) return reid_get_option(c, name, value);
-    if (n == "dt_ntrk") *value = o.dt_ntrk;
-    else if (n == "dt_split") *value = o.dt_split;
-    else if (n == "last_dt_split") *value = o.last_dt_split;
-    else if (n == "dt_status") *value = c->dt.xerr ? *c->dt.xerr : 0;       // 0 ok, 1 a split launch lost a partner, 2 an x3 forward clipped an operand; valid once the forward's stream is
-                                                                            // synchronised; cleared by busca_set_option("dt_status", 0) (an uncleared status is also returned by the next forward)
-    else if (n == "dt_tiled") *value = o.dt_tiled;
-    else if (n == "crop_band") *value = o.crop_band;
-    else if (n == "dt_exact_f32") *value = o.dt_exact_f32;
-    else if (n == "last_dt_grid") *value = o.last_dt_grid;
-    else if (n == "last_dt_ntrk") *value = o.last_dt_ntrk;
-    else return fail(c, BUSCA_EINVAL, "busca_get_option: unknown option '%s'", name);
+    if (!strncmp(name, "reid_", 5)) return reid_get_option(c, name, value);
+    // 0 ok, 1 a split launch lost a partner, 2 an x3 forward clipped an operand; valid once the forward's stream is synchronised; cleared by
+    // busca_set_option("dt_status", 0) (an uncleared status is also returned by the next forward)
+    if (!strcmp(name, "dt_status")) { *value = c->dt.xerr ? *c->dt.xerr : 0; return BUSCA_OK; }
+    const BuscaOptionDesc* e = option_by_name(name);
+    if (!e) return fail(c, BUSCA_EINVAL, "busca_get_option: unknown option '%s'", name);
+    *value = c->opt.*e->field;
     return BUSCA_OK;
 }
 

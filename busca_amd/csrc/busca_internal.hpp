@@ -24,7 +24,7 @@
 #pragma GCC visibility pop
 #include "dt_types.hpp"
 
-struct ReidState;                   // reid_kernel.hip.inc (complete only inside busca_reid.hip)
+struct ReidState;                   // reid_state.hip.inc (complete only inside busca_reid.hip)
 
 // ---------------------------------------------------------------------------------------------------------
 struct DTTiledW {                   // row-major copies of the matrices for the tiled path, in the operand type (f16 or f32)
@@ -51,6 +51,7 @@ struct DTState {
 
 // Developer options of one context.  Defaults come from the environment ONCE, when the context is created; afterwards they
 // change only through busca_set_option (so a test can flip a flavour between two forwards, and no forward calls getenv).
+// Environment variable and option name of each field: the table BUSCA_OPTIONS (busca_hip.hip), the list of record.
 struct BuscaOptions {
     int dt_ntrk = 0;          // BUSCA_DT_NTRK: tracks per workgroup of the f16 fused kernel (0 = automatic: 2 from B > 256, d = 256)
     int dt_tiled = 0;         // BUSCA_DT_TILED: force the layer-wise Decision-Transformer path
@@ -66,13 +67,6 @@ struct BuscaOptions {
                               // how the host re-runs a step whose x3 forward reported a clipped operand ("dt_status" 2)
     int crop_band = 1;        // BUSCA_CROP_BAND: 1 = crops through the LDS-staged band kernel (crop_band_kernel), 0 = one thread per output pixel (A/B, tests)
     int last_dt_grid = 0, last_dt_ntrk = 0, last_dt_split = 0;     // read-only: workgroups / tracks per workgroup / token-split tracks of the last fused launch
-    static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-    void from_env() {
-        dt_ntrk = env_int("BUSCA_DT_NTRK", 0); dt_tiled = getenv("BUSCA_DT_TILED") != nullptr ? 1 : 0;
-        dtl_rt = env_int("BUSCA_DTL_RT", 0); dtl_rt_mask = env_int("BUSCA_DTL_RT_MASK", -1);
-        dt_prof = env_int("BUSCA_DT_PROF", 0); dt_split = env_int("BUSCA_DT_SPLIT", -1);
-        dtl_ffn = env_int("BUSCA_DTL_FFN", 2); dtl_attn = env_int("BUSCA_DTL_ATTN", 1); crop_band = env_int("BUSCA_CROP_BAND", 1);
-    }
 };
 
 struct busca_ctx {

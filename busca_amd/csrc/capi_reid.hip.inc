@@ -1,782 +1,35 @@
-// C-ABI entry points of the ReID extractor: weight repacking, workspace, per-layer launch schedule.
+// C-ABI entry points of the ReID extractor's forward side (weights: reid_weights.hip.inc; the schedule behind them: reid_schedule.hip.inc).
 
-struct ReidSpec { int cout, cin, k, stride, pad; };
-
-// Forward order of the 53 convs (resnet.py:169-182, _make_layer :225-252): stem, then per bottleneck
-// conv1 1x1, conv2 3x3 (stride on the first block of layer2-4), conv3 1x1, [downsample 1x1 stride s].
-static std::vector<ReidSpec> reid_specs() {
-    std::vector<ReidSpec> v;
-    v.push_back({64, 3, 7, 2, 3});
-    const int nblk[4] = {3, 4, 6, 3}, planes[4] = {64, 128, 256, 512};
-    int inpl = 64;
-    for (int li = 0; li < 4; ++li)
-        for (int b = 0; b < nblk[li]; ++b) {
-            const int s = (b == 0 && li > 0) ? 2 : 1, p = planes[li];
-            v.push_back({p, inpl, 1, 1, 0});
-            v.push_back({p, p, 3, s, 1});
-            v.push_back({p * 4, p, 1, 1, 0});
-            if (b == 0) v.push_back({p * 4, inpl, 1, s, 0});
-            inpl = p * 4;
-        }
-    return v;
-}
-
-extern "C" size_t busca_reid_blob_floats(void) {
-    size_t n = 0;
-    for (const ReidSpec& s : reid_specs()) n += (size_t)s.cout * s.cin * s.k * s.k + 2 * (size_t)s.cout;
-    return n + 512 * 2048 + 512;
-}
-
-extern "C" int busca_reid_load_weights(busca_ctx* c, const float* blob, size_t blob_floats) {
-    return busca_reid_load_weights_ex(c, blob, blob_floats, BUSCA_PREC_F16);
-}
-
-extern "C" int busca_reid_load_weights_ex(busca_ctx* c, const float* blob, size_t blob_floats, int32_t precision) {
-    if (!c) return BUSCA_EINVAL;
-    if (!blob || blob_floats != busca_reid_blob_floats()) return fail(c, BUSCA_EINVAL, "ReID blob has %zu floats, expected %zu", blob_floats, busca_reid_blob_floats());
-    if (precision != BUSCA_PREC_F16 && precision != BUSCA_PREC_F32 && precision != BUSCA_PREC_F16X3) return fail(c, BUSCA_EINVAL, "bad ReID precision %d", precision);
-    HIP_TRY(c, hipSetDevice(c->device));
-    ReidState& R = *c->reid;
-    if (R.loaded) { HIP_TRY(c, hipDeviceSynchronize()); reid_free(R); }
-    R.prec = precision;
-    if (precision == BUSCA_PREC_F16X3) {
-        HIP_TRY(c, hipHostMalloc((void**)&R.xerr, sizeof(int), hipHostMallocMapped)); *R.xerr = 0;
-        HIP_TRY(c, hipHostGetDevicePointer((void**)&R.xerr_dev, R.xerr, 0));
-    }
-    if (const char* e = getenv("BUSCA_REID_GRAM")) R.gram_mode = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_HALO")) R.halo = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_FUSE_C1")) { R.fuse_c1 = atoi(e) != 0; if (atoi(e) > 0) R.fuse_c1_layers = std::min(3, std::max(1, atoi(e))); }
-    if (const char* e = getenv("BUSCA_REID_HALO_MIN")) R.halo_min_blocks = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_HALO_HALF")) R.halo_half_blocks = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_HALO_WPX")) R.halo_wpx = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_HALO_WPX_MIN")) R.halo_wpx_min = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_FUSE_C1_SMALL")) R.fuse_c1_small = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_GRAM_MIN")) R.gram_min_pixels = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_DIRECT_ROWS")) R.direct_rows = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_STATS2")) R.two_launch_stats = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_FUSE_DS_LAYERS")) R.fuse_ds_layers = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_KWAVE_BLOCKS")) R.kwave_blocks = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_PIPE_MIN")) R.pipe_min_tiles = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_PIPE_ALL")) R.pipe_all = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_PIPE_HALF")) R.pipe_half_blocks = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_KWAVE_HALO")) R.kwave_halo_blocks = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_KWAVE_MB")) R.kwave_max_mb = atof(e);
-    if (const char* e = getenv("BUSCA_REID_KWAVE_NW")) R.kwave_nw = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_KWAVE_PT")) R.kwave_pt = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_X3_MERGE_LAYERS")) R.x3_merge_layers = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_X3_HALF")) R.x3_half_blocks = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_X3_PTAIL")) R.x3_ptail_min = atoi(e);
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) R.num_cu = prop.multiProcessorCount; }
-    if (const char* e = getenv("BUSCA_REID_X3_GRAM")) R.x3_gram = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_X3_GRAM_MIN")) R.x3_gram_min = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_X3_MERGE_IN")) R.x3_merge_in = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_X3_FUSE_C1")) R.x3_fuse_c1 = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_X3_ROW3")) R.x3_row3 = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_X3_STEM_HALO")) R.x3_stem_halo = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_X3_STEM_U8")) R.x3_stem_u8 = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_X3_STEM_POOL")) R.x3_stem_pool = atoi(e) != 0;
-    if (const char* e = getenv("BUSCA_REID_X3_NARROW3")) R.x3_narrow3 = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_X3_FUSE_C1_MIN")) R.x3_fuse_c1_min = atoi(e);
-    if (const char* e = getenv("BUSCA_REID_X3_MERGE_IN_MIN")) R.x3_merge_in_min = atoi(e);
-    std::vector<_Float16> hx3;        // F16X3: hi / lo fragment-ordered weights
-    std::vector<float> hw;            // packed conv weights as floats (converted to fp16 below when needed)
-    std::vector<float> hf;
-    std::vector<_Float16> hpk;        // fragment-packed 3x3 weights
-    std::vector<_Float16> hkw;        // fragment-packed copies of every non-stem conv for conv_kwave_kernel
-    size_t ss_total = 0;
-    const float* cur = blob;
-    for (const ReidSpec& s : reid_specs()) {
-        ReidConv cv{s.cout, s.cin, s.k, s.stride, s.pad, 0, 0, 0, 0};
-        const float* W = cur; cur += (size_t)s.cout * s.cin * s.k * s.k;   // torch layout [co][ci][kh][kw]
-        while (hw.size() % 8) hw.push_back(0.f);                            // 16-byte aligned rows in either precision
-        cv.w_off = hw.size();
-        if (s.cin == 3) {                                                   // stem -> [64][7][8][4], RGB channel order kept
-            for (int co = 0; co < s.cout; ++co)
-                for (int kh = 0; kh < 7; ++kh)
-                    for (int kw = 0; kw < 8; ++kw)
-                        for (int ci = 0; ci < 4; ++ci)
-                            hw.push_back((kw < 7 && ci < 3) ? W[((size_t)(co * 3 + ci) * 7 + kh) * 7 + kw] : 0.f);
-        } else {
-            for (int co = 0; co < s.cout; ++co)
-                for (int kh = 0; kh < s.k; ++kh)
-                    for (int kw = 0; kw < s.k; ++kw)
-                        for (int ci = 0; ci < s.cin; ++ci)
-                            hw.push_back(W[((size_t)(co * s.cin + ci) * s.k + kh) * s.k + kw]);
-        }
-        const bool pk3 = s.k == 3 && s.stride == 1 && s.cin % 64 == 0 && (s.cout == 64 || s.cout == 128 || s.cout == 256);
-        const bool pk1 = s.k == 1 && ((s.cin == 256 && (s.cout == 64 || s.cout == 128)) || (s.cin == 512 && (s.cout == 128 || s.cout == 256)) ||
-                                       (s.cin == 1024 && (s.cout == 256 || s.cout == 512)));   // conv1 fused into the layer-1/2/3 tails
-        if (precision == BUSCA_PREC_F16 && (pk3 || pk1)) {
-            // fragment order for conv3x3_halo_kernel / tail_conv1_kernel: [Cout/16][step = chunk*taps + tap][kk][lane = 16b + a][8]:
-            //   W[co = 16ct + a][kh][kw][ci = chunk*64 + kk*32 + 8b + e]
-            cv.wpk_off = hpk.size();
-            const int taps = s.k * s.k, nsteps = (s.cin / 64) * taps;
-            hpk.resize(hpk.size() + (size_t)s.cout * s.cin * taps);
-            _Float16* dst = hpk.data() + cv.wpk_off;
-            for (int ct = 0; ct < s.cout / 16; ++ct)
-                for (int st = 0; st < nsteps; ++st)
-                    for (int kk = 0; kk < 2; ++kk)
-                        for (int ln = 0; ln < 64; ++ln)
-                            for (int e = 0; e < 8; ++e) {
-                                const int a = ln & 15, b = ln >> 4, chunk = st / taps, tap = st % taps;
-                                const int co = 16 * ct + a, ci = chunk * 64 + kk * 32 + 8 * b + e;
-                                dst[((((size_t)ct * nsteps + st) * 2 + kk) * 64 + ln) * 8 + e] = (_Float16)hw[cv.w_off + ((size_t)co * taps + tap) * s.cin + ci];
-                            }
-        }
-        if (precision == BUSCA_PREC_F16 && s.cin % 64 == 0 && s.cout % 64 == 0) {
-            // fragment order for conv_kwave_kernel: [Cout/16][half step h = 2 (tap*chunks + chunk) + kk][lane = 16b + a][8] =
-            //   W[co = 16ct + a][tap][ci = chunk*64 + kk*32 + 8b + e]  - a wave fetches an MFMA operand as 1 KiB of contiguous memory
-            cv.wkw_off = hkw.size();
-            const int taps = s.k * s.k, cch = s.cin / 64, nhalf = 2 * taps * cch;
-            hkw.resize(hkw.size() + (size_t)s.cout * s.cin * taps);
-            _Float16* dst = hkw.data() + cv.wkw_off;
-            for (int ct = 0; ct < s.cout / 16; ++ct)
-                for (int h = 0; h < nhalf; ++h)
-                    for (int ln = 0; ln < 64; ++ln)
-                        for (int e = 0; e < 8; ++e) {
-                            const int a = ln & 15, b = ln >> 4, st = h >> 1, kk = h & 1, tap = st / cch, chunk = st % cch;
-                            const int co = 16 * ct + a, ci = chunk * 64 + kk * 32 + 8 * b + e;
-                            dst[(((size_t)ct * nhalf + h) * 64 + ln) * 8 + e] = (_Float16)hw[cv.w_off + ((size_t)co * taps + tap) * s.cin + ci];
-                        }
-        }
-        if (precision == BUSCA_PREC_F16X3) {
-            // [Cout/16][half step h][hi, lo][lane = 16b + a][8]: W'[co = 16ct + a][k(h, b, e)], W' = W * 2^kc[co] with max |W'| in [2^12, 2^13)
-            //   convs: h = 2 (tap * chunks + chunk) + kk, k = (tap, ci = chunk*64 + kk*32 + 8b + e)
-            //   stem:  h = kernel row kh (0..7, row 7 zero), k = (tap kw = 2b + (e >> 2), channel e & 3)   - the [64][7][8][4] layout above
-            const bool stem = s.cin == 3;
-            const int taps = s.k * s.k, cch = stem ? 1 : s.cin / 64, nhalf = stem ? 8 : 2 * taps * cch;
-            const size_t krow = stem ? 224 : (size_t)taps * s.cin;
-            cv.wx3_off = hx3.size();
-            hx3.resize(hx3.size() + (size_t)s.cout * nhalf * 32 * 2);
-            cv.inv_off = hf.size();
-            hf.resize(hf.size() + s.cout);
-            _Float16* dst = hx3.data() + cv.wx3_off;
-            for (int co = 0; co < s.cout; ++co) {
-                float m = 0.f;
-                for (size_t k = 0; k < krow; ++k) m = std::max(m, std::fabs(hw[cv.w_off + (size_t)co * krow + k]));
-                int ex = 0, kc = 0;
-                if (m > 0.f && std::isfinite(m)) { std::frexp(m, &ex); kc = std::min(40, std::max(-40, 13 - ex)); }
-                hf[cv.inv_off + co] = std::ldexp(1.0f, -kc) / X3_XS;
-                const int ct = co / 16, a = co % 16;
-                for (int h = 0; h < nhalf; ++h)
-                    for (int b = 0; b < 4; ++b)
-                        for (int e = 0; e < 8; ++e) {
-                            float w;
-                            if (stem) w = h < 7 ? hw[cv.w_off + ((size_t)(co * 7 + h) * 8 + 2 * b + (e >> 2)) * 4 + (e & 3)] : 0.f;
-                            else { const int st = h >> 1, kk = h & 1, tap = st / cch, chunk = st % cch; w = hw[cv.w_off + ((size_t)co * taps + tap) * s.cin + chunk * 64 + kk * 32 + 8 * b + e]; }
-                            const float ws = std::ldexp(w, kc);
-                            const _Float16 hi = (_Float16)ws, lo = (_Float16)(ws - (float)hi);
-                            const size_t base = (((size_t)ct * nhalf + h) * 2) * 512 + (size_t)(16 * b + a) * 8 + e;
-                            dst[base] = hi; dst[base + 512] = lo;
-                        }
-            }
-        }
-        if (s.cin == 3)
-            for (int co = 0; co < 64; ++co) if (cur[co] < 0.f) R.stem_negmask |= 1ull << co;      // sign of the stem BatchNorm's gamma
-        cv.g_off = hf.size(); hf.insert(hf.end(), cur, cur + s.cout); cur += s.cout;
-        cv.b_off = hf.size(); hf.insert(hf.end(), cur, cur + s.cout); cur += s.cout;
-        cv.ss_off = ss_total; ss_total += 2 * (size_t)s.cout;
-        R.convs.push_back(cv);
-    }
-    if (precision == BUSCA_PREC_F16) {
-        // stem: fragment-ordered weights [4][7][64][8] from the [64][7][8][4] layout, and the byte -> normalised fp16 table
-        const ReidConv& c0 = R.convs[0];
-        R.stem_wpk_off = hpk.size();
-        for (int ct = 0; ct < 4; ++ct)
-            for (int kh = 0; kh < 7; ++kh)
-                for (int ln = 0; ln < 64; ++ln)
-                    for (int e = 0; e < 8; ++e) {
-                        const int a = ln & 15, b = ln >> 4;
-                        hpk.push_back((_Float16)hw[c0.w_off + ((size_t)((16 * ct + a) * 7 + kh) * 8 + 2 * b) * 4 + e]);
-                    }
-        R.stem_lut_off = hpk.size();
-        const double mean[3] = {0.406, 0.456, 0.485}, stdv[3] = {0.225, 0.224, 0.299};   // BGR, network.py:470-476
-        for (int ch = 0; ch < 3; ++ch)
-            for (int v = 0; v < 256; ++v) {
-                float x = (float)v / 255.0f;
-                x = (float)((double)x - mean[ch]);
-                hpk.push_back((_Float16)(float)((double)x / stdv[ch]));
-            }
-    }
-    R.red_w_off = hf.size();
-    hf.resize(hf.size() + (size_t)2048 * 512);
-    for (int o = 0; o < 512; ++o)
-        for (int k = 0; k < 2048; ++k) hf[R.red_w_off + (size_t)k * 512 + o] = cur[(size_t)o * 2048 + k];
-    cur += (size_t)512 * 2048;
-    R.red_b_off = hf.size(); hf.insert(hf.end(), cur, cur + 512);
-    if (precision == BUSCA_PREC_F16) {
-        std::vector<_Float16> h16(hw.size());
-        for (size_t i = 0; i < hw.size(); ++i) h16[i] = (_Float16)hw[i];
-        HIP_TRY(c, hipMalloc(&R.d_w, h16.size() * sizeof(_Float16)));
-        HIP_TRY(c, hipMemcpy(R.d_w, h16.data(), h16.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    } else {
-        HIP_TRY(c, hipMalloc(&R.d_w, hw.size() * sizeof(float)));
-        HIP_TRY(c, hipMemcpy(R.d_w, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (!hpk.empty()) {
-        HIP_TRY(c, hipMalloc((void**)&R.d_wpk, hpk.size() * sizeof(_Float16)));
-        HIP_TRY(c, hipMemcpy(R.d_wpk, hpk.data(), hpk.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (!hkw.empty()) {
-        HIP_TRY(c, hipMalloc((void**)&R.d_wkw, hkw.size() * sizeof(_Float16)));
-        HIP_TRY(c, hipMemcpy(R.d_wkw, hkw.data(), hkw.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (!hx3.empty()) {
-        HIP_TRY(c, hipMalloc((void**)&R.d_wx3, hx3.size() * sizeof(_Float16)));
-        HIP_TRY(c, hipMemcpy(R.d_wx3, hx3.data(), hx3.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-        // the stem's byte table: exactly reid_preprocess_f32_kernel's arithmetic per (channel, byte), x 2^6, clamped, split as x3_split2 splits
-        std::vector<unsigned> lut(768);
-        const double mean[3] = {0.406, 0.456, 0.485}, stdv[3] = {0.225, 0.224, 0.299};   // BGR, network.py:470-476
-        for (int ch = 0; ch < 3; ++ch)
-            for (int v = 0; v < 256; ++v) {
-                float x = (float)v / 255.0f;
-                x = (float)((double)x - mean[ch]);
-                x = (float)((double)x / stdv[ch]);
-                float t = x * X3_XS;
-                t = t < -X3_XMAX ? -X3_XMAX : (t > X3_XMAX ? X3_XMAX : t);
-                const _Float16 hi = (_Float16)t, lo = (_Float16)(t - (float)hi);
-                unsigned short hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-                lut[ch * 256 + v] = (unsigned)hb | ((unsigned)lb << 16);
-            }
-        HIP_TRY(c, hipMalloc((void**)&R.d_x3_lut, 768 * 4));
-        HIP_TRY(c, hipMemcpy(R.d_x3_lut, lut.data(), 768 * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(c, hipMalloc((void**)&R.d_f, hf.size() * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&R.d_ss, ss_total * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&R.d_zero, 256));
-    HIP_TRY(c, hipMemset(R.d_zero, 0, 256));
-    if (ss_total != (size_t)2 * 26560) return fail(c, BUSCA_EINVAL, "internal: BN channel count %zu", ss_total / 2);
-    HIP_TRY(c, hipMemcpy(R.d_f, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
-    R.loaded = true;
-    return BUSCA_OK;
-}
-
-// workspace plan (halves per crop unless noted)
-namespace reid_ws {
-constexpr size_t IN4 = 384 * 128 * 4, STEM = 192 * 64 * 64, X0 = 96 * 32 * 64, R1 = 96 * 32 * 128, R2 = 96 * 32 * 64,
-                 R3 = 96 * 32 * 256, RD = R3, XA = R3, XB = R3;
-constexpr size_t HALVES = IN4 + STEM + X0 + R1 + R2 + R3 + RD + XA + XB;
-constexpr size_t PART_FLOATS = 49152;         // per crop: max over convs of gridM*2*Cout / n (32-pixel tiles of conv_kwave_kernel: 96 x 2 x 256)
-constexpr size_t TICKET_BYTES = 64 * (32 + 128) * 4;   // arrival counters (zero between launches): [conv][64-channel column] of bn_reduce_finalize_kernel, then [conv][16-channel group] of bn_quadform_kernel
-constexpr size_t GRAM_PART_FLOATS = (size_t)24 << 20;  // chunk partials of one Gram pass (see gram_plan; weighted passes use shorter chunks: one crop at most)
-constexpr size_t GRAM_G_DOUBLES = 512 * 512 + 512 + 8 * 2 * 2048;     // G, sum vector, quadratic-form partials [8][2][Cout]
-constexpr size_t X3_GRAM_PART_DOUBLES = (size_t)512 * (64 * 64 + 64) > (size_t)256 * (128 * 128 + 128) ? (size_t)512 * (64 * 64 + 64) : (size_t)256 * (128 * 128 + 128);   // x3_gram_kernel partials
-constexpr size_t X3_GRAM_G_DOUBLES = 128 * 128 + 128 + 2 * 2048;
-inline size_t bytes(int n, size_t es = 2) {
-    const size_t nn = n < 1 ? 1 : n;
-    return TICKET_BYTES + nn * HALVES * es + 24 * 256 + (nn * PART_FLOATS + 2 * 2 * 2048 + nn * 2048 + nn * 512 + 2 * 26560) * 4 + (size_t)64 * 2 * 2048 * 8 +
-           (es == 2 ? GRAM_PART_FLOATS * 4 + GRAM_G_DOUBLES * 8 : (X3_GRAM_PART_DOUBLES + X3_GRAM_G_DOUBLES) * 8 + 512);
-}
-}
 extern "C" size_t busca_reid_workspace_bytes(int32_t n) { return reid_ws::bytes(n, 2); }   // fp16 flavour; f32 needs 2x the activation part
 
-// ---- statistics through the Gram matrix (reid_gram.hip.inc) ------------------------------------------------------
-struct GramPlan { int cw, ngroups, npairs, steps, nchunks; };
-static GramPlan gram_plan(int M, int Cin, int align_px = 0) {
-    GramPlan p;
-    p.cw = Cin == 128 ? 8 : 4;                                           // 128-wide tiles only where one group covers Cin (no spare registers for two)
-    p.ngroups = Cin / (16 * p.cw);
-    p.npairs = p.ngroups * (p.ngroups + 1) / 2;
-    const int wsteps = (M + 127) / 128;                                  // rounds of 4 waves x 32 pixels
-    // CW 8 holds 288 accumulator registers and 132 KB of LDS: one workgroup per CU, so one wave of workgroups
-    const int target = std::max(1, (p.cw == 8 ? 256 : 768) / p.npairs);
-    p.steps = (wsteps + target - 1) / target;
-    if (align_px > 0) {                                                  // weighted statistics: a chunk (128 steps pixels) must not straddle two crops
-        const int per = align_px / 128;                                  // 128-pixel rounds per crop (the caller checked align_px % 128 == 0)
-        p.steps = std::max(1, std::min(p.steps, per));
-        while (per % p.steps) --p.steps;
-    }
-    p.nchunks = (wsteps + p.steps - 1) / p.steps;
-    return p;
-}
-static bool gram_fits(int M, int Cin, int align_px) {
-    const GramPlan p = gram_plan(M, Cin, align_px);
-    return (size_t)p.nchunks * p.npairs * (size_t)(16 * p.cw) * (16 * p.cw) <= reid_ws::GRAM_PART_FLOATS;
-}
-// `ohw`: output pixels per crop of the bottleneck (M = crops x ohw)
-static bool reid_use_gram(const ReidState& R, int layer, int M, int ohw) {
-    if (R.prec != BUSCA_PREC_F16 || layer > 2) return false;            // layer4: M ~ Cin, the quadratic form costs more than it saves
-    if (R.cur_wts != nullptr && layer > 1) return false;                // weighted statistics (Gram chunks inside one crop): 3072 / 768 pixels per crop in layers 1-2 are multiples of 128, layer 3's 192 are not
-    const bool use = R.gram_mode >= 0 ? R.gram_mode >= 1 : M >= R.gram_min_pixels;
-    if (!use) return false;
-    // a weighted pass cuts its chunks at crop boundaries (nchunks ~ crops): beyond ~600 distinct crops the chunk partials of a 256-channel
-    // input no longer fit the scratch - take the direct-statistics schedule then (conv3's input has 64 << layer channels, the first
-    // block's downsample input 64 / 256 / 512)
-    const int al = R.cur_wts != nullptr ? ohw : 0;
-    return gram_fits(M, 64 << layer, al) && gram_fits(M, layer == 0 ? 64 : 128 << layer, al);
-}
-// BN (scale, shift) of a 1x1 conv (stride `stride`, weights w [Cout][Cin] fp16) over an n x H x W x Cin input x, from x alone.
-static int gram_stats_launch(busca_ctx* c, hipStream_t s, const _Float16* x, const float* in_ss, int n, int H, int W, int Cin, int stride,
-                             const _Float16* w, int Cout, const float* gamma, const float* beta, float* gpart, double* gG, float* ss_out, int* qticket = nullptr,
-                             const float* wts = nullptr, double wsum = 0.0) {
-    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1, M = n * OH * OW;
-    if (wts != nullptr && (OH * OW) % 128) return fail(c, BUSCA_EINVAL, "weighted Gram statistics need a multiple of 128 pixels per crop (%d)", OH * OW);
-    const double invM = 1.0 / ((wts != nullptr ? wsum : (double)n) * (double)(OH * OW));
-    if ((Cin & (Cin - 1)) || Cin < 64 || Cin > 512 || Cout < QF_CPB || Cout % QF_CPB || Cout > 2048 || (stride != 1 && OW % 8))
-        return fail(c, BUSCA_EINVAL, "Gram statistics: unsupported shape (Cin %d, Cout %d, M %d)", Cin, Cout, M);
-    const GramPlan p = gram_plan(M, Cin, wts != nullptr ? OH * OW : 0);
-    const int gw = 16 * p.cw, tile = gw * gw;
-    if ((size_t)p.nchunks * p.npairs * tile > reid_ws::GRAM_PART_FLOATS)
-        return fail(c, BUSCA_EINVAL, "Gram statistics: unsupported shape (Cin %d, Cout %d, M %d)", Cin, Cout, M);
-    GramArgs g{};
-    g.x = x; g.in_ss = in_ss; g.M = M; g.Cin = Cin; g.OHW = OH * OW; g.OW = OW; g.HW = H * W; g.W = W; g.stride = stride;
-    g.steps = p.steps; g.ngroups = p.ngroups; g.nchunks = p.nchunks; g.npairs = p.npairs; g.partials = gpart;
-    double* gsum = gG + (size_t)512 * 512;
-    const size_t lds = (size_t)2 * tile * 4 + (size_t)2 * Cin * 4;
-    const size_t lds_max = (size_t)2 * tile * 4 + (size_t)2 * 512 * 4;   // the attribute is set once per kernel: use the largest Cin
-    const dim3 ggrid(((p.nchunks + 7) / 8) * 8 * p.npairs), rgrid(tile / 64, p.npairs);
-    if (p.cw == 4) {
-        if (p.ngroups == 1) hipLaunchKernelGGL((gram_kernel<4, false>), ggrid, dim3(256), lds, s, g);
-        else hipLaunchKernelGGL((gram_kernel<4, true>), ggrid, dim3(256), lds, s, g);
-        hipLaunchKernelGGL((gram_reduce_kernel<4>), rgrid, dim3(1024), 0, s, (const float*)gpart, p.nchunks, p.npairs, p.ngroups, Cin, gG, gsum, wts, 128 * p.steps, OH * OW);
-    } else {
-        { int rc = ensure_lds(c, (const void*)gram_kernel<8, false>, lds_max); if (rc) return rc; }
-        hipLaunchKernelGGL((gram_kernel<8, false>), ggrid, dim3(256), lds, s, g);
-        hipLaunchKernelGGL((gram_reduce_kernel<8>), rgrid, dim3(1024), 0, s, (const float*)gpart, p.nchunks, p.npairs, p.ngroups, Cin, gG, gsum, wts, 128 * p.steps, OH * OW);
-    }
-    const size_t qlds = ((size_t)16 * (Cin + 2) + 2 * 4 * 16) * 8;
-    { int rc = ensure_lds(c, (const void*)bn_quadform_kernel_t<_Float16>, ((size_t)16 * (512 + 2) + 2 * 4 * 16) * 8); if (rc) return rc; }
-    const int JS = Cin <= 128 ? 1 : Cin / 64;                            // tile-pair slices; small matrices finish inside the kernel
-    double* qpart = gsum + 512;                                          // [JS][2][Cout]
-    if (Cout / QF_CPB > 128) qticket = nullptr;
-    hipLaunchKernelGGL(bn_quadform_kernel_t<_Float16>, dim3(Cout / QF_CPB, JS), dim3(256), qlds, s, (const double*)gG, (const double*)gsum, w, Cin, Cout, qpart,
-                       invM, gamma, beta, ss_out, JS > 1 ? qticket : (int*)nullptr);
-    if (JS > 1 && qticket == nullptr) hipLaunchKernelGGL(bn_quadform_finalize_kernel, dim3((Cout + 255) / 256), dim3(256), 0, s, (const double*)qpart, JS, Cout, invM, gamma, beta, ss_out);
-    return BUSCA_OK;
-}
-static int reid_gram_stats(busca_ctx* c, hipStream_t s, const ReidState& R, int idx, const _Float16* x, const float* in_ss, int n, int H, int W,
-                           float* gpart, double* gG, float* ss_base) {
-    const ReidConv& cv = R.convs[idx];
-    if (cv.k != 1) return fail(c, BUSCA_EINVAL, "internal: Gram statistics on a %dx%d conv", cv.k, cv.k);
-    int* qt = (R.cur_tickets != nullptr && idx < 64 && !R.two_launch_stats) ? R.cur_tickets + 64 * 32 + idx * 128 : nullptr;
-    return gram_stats_launch(c, s, x, in_ss, n, H, W, cv.cin, cv.stride, (const _Float16*)R.d_w + cv.w_off, cv.cout, R.d_f + cv.g_off, R.d_f + cv.b_off,
-                             gpart, gG, ss_base + cv.ss_off, qt, R.cur_wts, R.cur_wsum);
-}
-
-// Stand-alone entry (unit tests, include/busca_hip.h): scratch is allocated per call.
+// Stand-alone entry (unit tests, include/busca_hip.h): scratch is allocated per call, and the pass holds nothing but it.
 extern "C" int busca_bn_stats_1x1(busca_ctx* c, const void* x, const float* in_ss, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t stride,
                                   const void* w, int32_t Cout, const float* gamma, const float* beta, float* ss_out, void* stream) {
     if (!c) return BUSCA_EINVAL;
     if (!x || !w || !gamma || !beta || !ss_out || n < 1 || H < 1 || W < 1 || stride < 1) return fail(c, BUSCA_EINVAL, "busca_bn_stats_1x1: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    float* gpart = nullptr; double* gG = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&gpart, reid_ws::GRAM_PART_FLOATS * 4));
-    if (hipMalloc((void**)&gG, reid_ws::GRAM_G_DOUBLES * 8) != hipSuccess) { hipFree(gpart); return fail(c, BUSCA_ENOMEM, "busca_bn_stats_1x1: scratch"); }
-    const int rc = gram_stats_launch(c, (hipStream_t)stream, (const _Float16*)x, in_ss, n, H, W, Cin, stride, (const _Float16*)w, Cout, gamma, beta, gpart, gG, ss_out);
-    hipStreamSynchronize((hipStream_t)stream);
-    hipFree(gpart); hipFree(gG);
+    ReidPass P;
+    P.s = (hipStream_t)stream; P.n = n;
+    HIP_TRY(c, hipMalloc((void**)&P.gpart, reid_ws::GRAM_PART_FLOATS * 4));
+    if (hipMalloc((void**)&P.gG, reid_ws::GRAM_G_DOUBLES * 8) != hipSuccess) { hipFree(P.gpart); return fail(c, BUSCA_ENOMEM, "busca_bn_stats_1x1: scratch"); }
+    const int rc = gram_stats_launch(c, P, {(const _Float16*)x, in_ss, H, W, Cin, stride, (const _Float16*)w, Cout, gamma, beta, ss_out, nullptr});
+    hipStreamSynchronize(P.s);
+    hipFree(P.gpart); hipFree(P.gG);
     if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
     return BUSCA_OK;
 }
-
-// BatchNorm (scale, shift) of conv `idx` from its per-tile statistics [gridM][2][cout]: ONE launch either way - the direct kernel
-// for few tiles, reduce + finalise-by-the-last-arriver beyond (tickets: [conv][64-channel column] words of the workspace).
-static void bn_finalize_launch(hipStream_t s, const ReidState& R, int idx, const float* partials, int gridM, double invM, double* red, float* ss_out) {
-    const ReidConv& cv = R.convs[idx];
-    const float* gamma = R.d_f + cv.g_off; const float* beta = R.d_f + cv.b_off;
-    if (gridM <= R.direct_rows) {
-        hipLaunchKernelGGL(bn_finalize_direct_kernel, dim3((cv.cout + 63) / 64), dim3(1024), 0, s, partials, gridM, cv.cout, invM, gamma, beta, ss_out);
-    } else if (R.cur_tickets != nullptr && idx < 64 && (cv.cout + 63) / 64 <= 32 && !R.two_launch_stats) {
-        hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((cv.cout + 63) / 64, BN_SLICES), dim3(256), 0, s, partials, gridM, cv.cout, red, R.cur_tickets + idx * 32, invM, gamma, beta, ss_out);
-    } else {
-        hipLaunchKernelGGL(bn_reduce_kernel, dim3((cv.cout + 63) / 64, BN_SLICES), dim3(256), 0, s, partials, gridM, cv.cout, red);
-        hipLaunchKernelGGL(bn_finalize_kernel, dim3((cv.cout + 255) / 256), dim3(256), 0, s, (const double*)red, cv.cout, invM, gamma, beta, ss_out);
-    }
-}
-
-// ---- F16X3 flavour (reid_x3.hip.inc): one kernel family for every conv ---------------------------------------------------------
-template <int WC, int WP, int CT, int PT, int STG, int KS, int EPI, int SK = 0>
-static int x3_launch_one(busca_ctx* c, hipStream_t s, const X3Args& a) {
-    constexpr int tables = (STG == X3_BN || STG == X3_POOLIN) ? 1 : STG == X3_MRG ? 2 : 0;
-    const size_t lds = x3_lds_bytes<WC, WP, CT, PT>(a.Cin, tables, EPI == X3_MERGE_C1, SK == 3 && STG == X3_BN, SK == 3 && STG == X3_STEM, EPI == X3_POOL);
-    { int rc = ensure_lds(c, (const void*)conv_x3_kernel<WC, WP, CT, PT, STG, KS, EPI, 0, SK>, x3_lds_bytes<WC, WP, CT, PT>(2048, tables, EPI == X3_MERGE_C1, SK == 3 && STG == X3_BN, SK == 3 && STG == X3_STEM, EPI == X3_POOL)); if (rc) return rc; }
-    const unsigned nb = (unsigned)(((a.gridM + 7) / 8) * 8 * a.gridN);
-    TimedLaunch tl(c, s);
-    hipLaunchKernelGGL((conv_x3_kernel<WC, WP, CT, PT, STG, KS, EPI, 0, SK>), dim3(nb), dim3(64 * WC * WP), lds, s, a);
-    return BUSCA_OK;
-}
-// BatchNorm (scale, shift) of 1x1 conv `idx` (C -> 4 C, C = 64 / 128) from the float32-equivalent Gram matrix of its input (x3_gram_kernel)
-template <int C>
-static int x3_gram_stats_c(busca_ctx* c, hipStream_t s, const ReidState& R, int idx, const float* x, const float* in_ss, int n, int ohw, double* part, double* G, float* ss_out) {
-    const ReidConv& cv = R.convs[idx];
-    const int M = n * ohw, ntiles = (M + 127) / 128;
-    const int nwg = std::min(ntiles, C == 64 ? 512 : 256);
-    X3GramArgs a{};
-    a.x = x; a.in_ss = in_ss; a.wts = R.cur_wts; a.part = part; a.M = M; a.OHW = ohw; a.ntiles = ntiles;
-    constexpr size_t lds = (size_t)2 * 128 * 2 * C + (size_t)C * 8;        // two row-major fp16 planes of the tile (the channel-sum scratch of the end reuses them), BatchNorm table
-    { int rc = ensure_lds(c, (const void*)x3_gram_kernel<C>, lds); if (rc) return rc; }
-    double* sum = G + (size_t)C * C;
-    double* qpart = sum + C;
-    {
-        TimedLaunch tl(c, s);
-        hipLaunchKernelGGL((x3_gram_kernel<C>), dim3(nwg), dim3(4 * C), lds, s, a);
-    }
-    hipLaunchKernelGGL((x3_gram_reduce_kernel<C>), dim3((C * C + C + 63) / 64), dim3(256), 0, s, (const double*)part, nwg, G, sum);
-    const size_t qlds = ((size_t)16 * (C + 2) + 2 * 4 * 16) * 8;
-    { int rc = ensure_lds(c, (const void*)bn_quadform_kernel_t<float>, ((size_t)16 * (512 + 2) + 2 * 4 * 16) * 8); if (rc) return rc; }
-    const double invM = 1.0 / (R.cur_wsum * (double)ohw);
-    hipLaunchKernelGGL(bn_quadform_kernel_t<float>, dim3(cv.cout / QF_CPB, 1), dim3(256), qlds, s, (const double*)G, (const double*)sum, (const float*)R.d_w + cv.w_off, C, cv.cout, qpart,
-                       invM, (const float*)(R.d_f + cv.g_off), (const float*)(R.d_f + cv.b_off), ss_out, (int*)nullptr);
-    return BUSCA_OK;
-}
-
-// Persistent fused tail (reid_x3p.hip.inc) of a 1x1 conv3 with 64 / 128 input channels: one workgroup per CU for the whole launch.  Returns -1 when the
-// shape is not one the kernel is built for (the caller then launches the one-shot kernel: same results bit for bit).
-template <int KC, int C1, int NW, bool W2P, bool W3P>
-static int x3_ptail_launch_one(busca_ctx* c, hipStream_t s, const ReidState& R, const X3PArgs& p) {
-    constexpr size_t lds = x3p_lds_bytes<KC, C1>();
-    { int rc = ensure_lds(c, (const void*)x3_ptail_kernel<KC, C1, NW, W2P, W3P>, lds); if (rc) return rc; }
-    const int per = 8 * p.gridN;
-    int nwg = (R.num_cu / per) * per;                   // a multiple of 8 x gridN: the workgroups of a pixel tile sit on one XCD
-    if (nwg <= 0) return -1;
-    TimedLaunch tl(c, s);
-    hipLaunchKernelGGL((x3_ptail_kernel<KC, C1, NW, W2P, W3P>), dim3(nwg), dim3(64 * NW), lds, s, p);
-    return BUSCA_OK;
-}
-static int x3_ptail_launch(busca_ctx* c, hipStream_t s, const ReidState& R, const X3Args& a) {
-    if (R.x3_ptail_min <= 0 || a.M % 128 != 0 || a.OHWo % 128 != 0 || a.Cout % 256 != 0 || a.in_ss == nullptr) return -1;
-    const int ntiles = a.M / 128, gridN = a.Cout / 256;
-    if ((long)ntiles * gridN < (long)R.x3_ptail_min || R.num_cu < 8 * gridN) return -1;
-    X3PArgs p{};
-    p.in = a.in; p.in_ss = a.in_ss; p.w = a.w; p.inv = a.inv; p.out = a.out; p.out_ss = a.out_ss; p.idt = a.idt; p.idt_ss = a.idt_ss;
-    p.c1_w = a.c1_w; p.c1_inv = a.c1_inv; p.c1_out = a.c1_out; p.partials = a.partials; p.wts = a.wts;
-    p.M = a.M; p.Cout = a.Cout; p.OHWo = a.OHWo; p.ntiles = ntiles; p.gridN = gridN;
-    if (a.Cin == 64 && a.Cout == 256 && a.c1_w != nullptr && a.c1_cout == 64) return x3_ptail_launch_one<1, 64, 4, true, true>(c, s, R, p);
-    if (a.Cin == 64 && a.Cout == 256 && a.c1_w != nullptr && a.c1_cout == 128) return x3_ptail_launch_one<1, 128, 4, false, false>(c, s, R, p);
-    if (a.Cin == 64 && a.c1_w == nullptr) return x3_ptail_launch_one<1, 0, 8, true, true>(c, s, R, p);
-    if (a.Cin == 128 && a.c1_w == nullptr) return x3_ptail_launch_one<2, 0, 8, true, true>(c, s, R, p);
-    return -1;
-}
-
-static int reid_x3_conv(busca_ctx* c, hipStream_t s, const ReidState& R, int idx, const float* in, const float* in_ss, int n, int H, int W,
-                        float* out, float* partials, double* red, float* ss_base, int* OHo, int* OWo, int mode, const float* idt, const float* idt_ss,
-                        const float* mrg_idt = nullptr, const float* mrg_idt_ss = nullptr, float* mrg_out = nullptr, int c1_idx = -1, float* c1_out = nullptr) {
-    const ReidConv& cv = R.convs[idx];
-    if (cv.wx3_off == (size_t)-1 || R.d_wx3 == nullptr) return fail(c, BUSCA_EINVAL, "internal: conv %d has no split-fp16 weights", idx);
-    const bool stem = cv.cin == 3;
-    X3Args a{};
-    a.in = in; a.in_ss = in_ss; a.w = R.d_wx3 + cv.wx3_off; a.inv = R.d_f + cv.inv_off; a.out = out; a.partials = partials; a.zero = (const float*)R.d_zero;
-    a.wts = R.cur_wts; a.out_ss = ss_base + cv.ss_off; a.idt = idt; a.idt_ss = idt_ss;
-    a.mrg_idt = mrg_idt; a.mrg_idt_ss = mrg_idt_ss; a.mrg_out = mrg_out;
-    if (stem && R.x3_stem_halo && R.cur_crops != nullptr) { a.stem_crops = R.cur_crops; a.stem_zero = R.cur_zn; a.stem_lut = R.d_x3_lut; }
-    const bool pool_out = stem && R.x3_stem_halo && R.cur_pool_q != nullptr && mode == CONV_NORMAL;                  // the stem writes the pooled parts instead of its raw map (`out` = P)
-    const bool pool_in = !stem && R.cur_pool_q != nullptr && in == R.cur_pool_p && in_ss != nullptr && cv.k == 1 && cv.stride == 1 && cv.cin == 64 && mode == CONV_NORMAL;
-    if (pool_out) { a.pool_gamma = R.d_f + cv.g_off; a.pool_p = out; a.pool_q = R.cur_pool_q; }
-    if (pool_in) a.pool_q = R.cur_pool_q;
-    if (!stem && R.cur_pool_q != nullptr && in == R.cur_pool_p && !pool_in) return fail(c, BUSCA_EINVAL, "internal: conv %d cannot read the pooled stem parts", idx);
-    if (mrg_out != nullptr && !(cv.k == 1 && cv.stride == 1 && in_ss && mrg_idt && mode == CONV_NORMAL && cv.cout % 256 == 0))
-        return fail(c, BUSCA_EINVAL, "internal: conv %d cannot form its input from the previous block's tail", idx);
-    a.H = H; a.W = W; a.Cin = stem ? 4 : cv.cin; a.Cout = cv.cout; a.stride = cv.stride; a.pad = cv.pad;
-    a.OH = (H + 2 * cv.pad - cv.k) / cv.stride + 1; a.OW = (W + 2 * cv.pad - cv.k) / cv.stride + 1;
-    a.M = n * a.OH * a.OW; a.OHWo = a.OH * a.OW;
-    a.gridM = (a.M + 127) / 128;
-    if (c1_idx >= 0) {
-        // fused tail + the next bottleneck's conv1 (X3_MERGE_C1): one channel block of 256, 128-pixel tiles
-        const ReidConv& cn = R.convs[c1_idx];
-        if (!(mode == CONV_MERGE && cv.k == 1 && cv.cout == 256 && in_ss && cn.k == 1 && cn.stride == 1 && cn.cin == 256 && (cn.cout == 64 || cn.cout == 128) && cn.wx3_off != (size_t)-1 && c1_out))
-            return fail(c, BUSCA_EINVAL, "internal: conv %d cannot carry conv %d in its tail", idx, c1_idx);
-        a.c1_w = R.d_wx3 + cn.wx3_off; a.c1_inv = R.d_f + cn.inv_off; a.c1_out = c1_out; a.c1_cout = cn.cout; a.gridN = 1;
-        int rc = x3_ptail_launch(c, s, R, a);
-        if (rc < 0) rc = x3_launch_one<8, 1, 2, 8, X3_BN, 1, X3_MERGE_C1>(c, s, a);
-        if (rc) return rc;
-        *OHo = a.OH; *OWo = a.OW;
-        bn_finalize_launch(s, R, c1_idx, partials, a.gridM, 1.0 / (R.cur_wsum * (double)(a.OH * a.OW)), red, ss_base + cn.ss_off);
-        return BUSCA_OK;
-    }
-    const int epi = mode == CONV_NORMAL ? X3_RAW : mode == CONV_STATS_ONLY ? X3_STATS : X3_MERGE;
-    if (mode != CONV_NORMAL && mode != CONV_STATS_ONLY && mode != CONV_MERGE) return fail(c, BUSCA_EINVAL, "internal: split-fp16 conv mode %d", mode);
-    // 3x3, stride 1, 128-pixel tiles made of whole image rows (layers 1-2): one staging per kernel row serves its three taps (conv_x3_kernel ROW3)
-    const bool row3_any = R.x3_row3 > 0 && cv.k == 3 && cv.stride == 1 && cv.pad == 1 && (a.OW == 8 || a.OW == 16 || a.OW == 32) && cv.cin % 64 == 0 && (cv.cin & (cv.cin - 1)) == 0 && in_ss;
-    const bool row3 = row3_any && (a.OH * a.OW) % 128 == 0 && a.OW >= 16;
-    const bool row3_64 = row3_any && R.x3_row3 >= 2 && (a.OH * a.OW) % 64 == 0 && cv.cout % 256 == 0 && epi == X3_RAW;     // 64-pixel tiles (layers 3-4: 24 x 8 maps)
-    int rc = BUSCA_EINVAL;
-    if (stem) { a.gridN = 1; rc = pool_out ? x3_launch_one<2, 2, 2, 4, X3_STEM, 7, X3_POOL, 3>(c, s, a) : R.x3_stem_halo ? x3_launch_one<2, 2, 2, 4, X3_STEM, 7, X3_RAW, 3>(c, s, a) : x3_launch_one<2, 2, 2, 4, X3_STEM, 7, X3_RAW>(c, s, a); }
-    else if (cv.cout % 256 == 0 && cv.k == 3 && in_ss && epi == X3_RAW && R.x3_narrow3 > 0 && ((a.M + 63) / 64) * (cv.cout / 256) < R.x3_narrow3) {
-        // small batches: the 3x3 convs of layers 3-4 on four-wave workgroups of 64 pixels x 128 channels, two per CU (a workgroup's serial K loop sets the
-        // duration of such a launch; twice the workgroups, each with half the products per step)
-        a.gridN = cv.cout / 128; a.gridM = (a.M + 63) / 64;
-        rc = x3_launch_one<4, 1, 2, 4, X3_BN, 3, X3_RAW>(c, s, a);
-    }
-    else if (row3_64 && !(R.x3_narrow3 > 0 && ((a.M + 63) / 64) * (cv.cout / 256) < R.x3_narrow3)) {
-        a.gridN = cv.cout / 256; a.gridM = (a.M + 63) / 64;
-        rc = x3_launch_one<8, 1, 2, 4, X3_BN, 3, X3_RAW, 3>(c, s, a);
-    }
-    else if (cv.cout % 256 == 0) {
-        a.gridN = cv.cout / 256;
-        // launches that would not fill the chip twice run on 64-pixel tiles (twice the workgroups, each with half the serial K loop's work):
-        // tracker-sized batches (40-150 crops) put layers 3-4 at 30-230 tiles of 128 pixels
-        // x3_half_blocks < 0 (default): whichever tile height takes fewer ROUNDS of one-workgroup-per-CU launches, a 64-pixel round priced at 0.52 of a
-        // 128-pixel one (measured: layer 3's 3x3 94 / 48 us per round): 88 crops put layer 3 at 132 tiles of 128 pixels = ONE round, where 264 tiles of 64
-        // pixels take two (88 crops 4.70 -> 4.59 ms, 150 crops 6.34 -> 6.15)
-        bool half = a.gridM * a.gridN < R.x3_half_blocks;
-        if (R.x3_half_blocks < 0) {
-            const long t128 = (long)a.gridM * a.gridN, t64 = (long)((a.M + 63) / 64) * a.gridN, ncu = R.num_cu > 0 ? R.num_cu : 256;
-            half = t128 < 2 * ncu && (double)((t64 + ncu - 1) / ncu) * 0.52 < (double)((t128 + ncu - 1) / ncu);       // (beyond two rounds the 64-pixel tiles measured equal or slower)
-        }
-        if (half) a.gridM = (a.M + 63) / 64;
-#define X3_L(S_, K_, E_) (half ? x3_launch_one<8, 1, 2, 4, S_, K_, E_>(c, s, a) : x3_launch_one<8, 1, 2, 8, S_, K_, E_>(c, s, a))
-        if (pool_in) rc = X3_L(X3_POOLIN, 1, X3_RAW);
-        else if (mrg_out != nullptr) rc = X3_L(X3_MRG, 1, X3_RAW);
-        else if (cv.k == 3 && in_ss && epi == X3_RAW) rc = X3_L(X3_BN, 3, X3_RAW);
-        else if (cv.k == 1 && in_ss && epi == X3_RAW) rc = X3_L(X3_BN, 1, X3_RAW);
-        else if (cv.k == 1 && in_ss && epi == X3_STATS) rc = X3_L(X3_BN, 1, X3_STATS);
-        else if (cv.k == 1 && in_ss && epi == X3_MERGE) {
-            rc = cv.stride == 1 ? x3_ptail_launch(c, s, R, a) : -1;         // layers 1-2, large batches: persistent workgroups (same results bit for bit)
-            if (rc < 0) rc = X3_L(X3_BN, 1, X3_MERGE);
-        }
-        else if (cv.k == 1 && !in_ss && epi == X3_RAW) rc = X3_L(X3_PLAIN, 1, X3_RAW);
-#undef X3_L
-    } else if (cv.cout == 128 && epi == X3_RAW) {
-        a.gridN = 1;
-        if (cv.k == 3 && in_ss && row3) rc = x3_launch_one<4, 1, 2, 8, X3_BN, 3, X3_RAW, 3>(c, s, a);
-        else if (cv.k == 3 && in_ss) rc = x3_launch_one<4, 1, 2, 8, X3_BN, 3, X3_RAW>(c, s, a);
-        else if (cv.k == 1 && !in_ss) rc = x3_launch_one<4, 1, 2, 8, X3_PLAIN, 1, X3_RAW>(c, s, a);
-    } else if (cv.cout == 64 && epi == X3_RAW) {
-        a.gridN = 1;
-        if (pool_in) rc = x3_launch_one<2, 2, 2, 4, X3_POOLIN, 1, X3_RAW>(c, s, a);
-        else if (cv.k == 3 && in_ss && row3 && R.x3_ptail_min > 0 && cv.cin == 64 && a.OW == 32 && a.OH % 4 == 0 && a.M % 128 == 0 && a.M / 128 >= 16) {
-            // layer 1's stride-1 3x3 convs: persistent halo-resident workgroups, weights in registers (x3_p3x3_kernel; the one-shot ROW3 kernel's results bit for bit)
-            X3P3Args p{};
-            p.in = a.in; p.in_ss = a.in_ss; p.w = a.w; p.inv = a.inv; p.out = a.out; p.partials = a.partials; p.wts = a.wts;
-            p.M = a.M; p.OH = a.OH; p.OHWo = a.OHWo; p.ntiles = a.M / 128;
-            rc = ensure_lds(c, (const void*)x3_p3x3_kernel, x3p3_lds_bytes());
-            if (!rc) {
-                TimedLaunch tl(c, s);
-                hipLaunchKernelGGL(x3_p3x3_kernel, dim3(std::min(p.ntiles, R.num_cu)), dim3(256), x3p3_lds_bytes(), s, p);
-            }
-        }
-        else if (cv.k == 3 && in_ss && row3) rc = x3_launch_one<2, 2, 2, 4, X3_BN, 3, X3_RAW, 3>(c, s, a);
-        else if (cv.k == 3 && in_ss) rc = x3_launch_one<2, 2, 2, 4, X3_BN, 3, X3_RAW>(c, s, a);
-        else if (cv.k == 1 && !in_ss) rc = x3_launch_one<2, 2, 2, 4, X3_PLAIN, 1, X3_RAW>(c, s, a);
-    }
-    if (rc == BUSCA_EINVAL) return fail(c, BUSCA_EINVAL, "internal: no split-fp16 kernel for conv %d (k %d, %d -> %d, %s input, mode %d)", idx, cv.k, cv.cin, cv.cout, in_ss ? "raw" : "final", mode);
-    if (rc) return rc;
-    *OHo = a.OH; *OWo = a.OW;
-    if (mode == CONV_MERGE) return BUSCA_OK;
-    bn_finalize_launch(s, R, idx, partials, a.gridM, 1.0 / (R.cur_wsum * (double)(a.OH * a.OW)), red, ss_base + cv.ss_off);
-    return BUSCA_OK;
-}
-
-template <typename T>
-static int reid_conv_launch(busca_ctx* c, hipStream_t s, const ReidState& R, int idx, const T* in, const float* in_ss,
-                            int n, int H, int W, T* out, float* partials, double* red, float* ss_base, int* OHo, int* OWo,
-                            int mode = CONV_NORMAL, const T* idt = nullptr, const float* idt_ss = nullptr,
-                            int ds_idx = -1, const T* ds_in = nullptr, int dsH = 0, int dsW = 0, const float* ds_in_ss = nullptr,
-                            const T* mrg_idt = nullptr, const float* mrg_idt_ss = nullptr, T* mrg_out = nullptr, int c1_idx = -1, T* c1_out = nullptr) {
-    const ReidConv& cv = R.convs[idx];
-    if (sizeof(T) == 4 && R.prec == BUSCA_PREC_F16X3)
-        return reid_x3_conv(c, s, R, idx, (const float*)in, in_ss, n, H, W, (float*)out, partials, red, ss_base, OHo, OWo, mode, (const float*)idt, idt_ss,
-                            (const float*)mrg_idt, mrg_idt_ss, (float*)mrg_out, c1_idx, (float*)c1_out);
-    if (mrg_out != nullptr) return fail(c, BUSCA_EINVAL, "internal: deferred block tail outside the split-fp16 flavour");
-    float* ss_out = ss_base + cv.ss_off;
-    ConvArgs g{};
-    g.in = (const _Float16*)in; g.w = (const _Float16*)((const T*)R.d_w + cv.w_off); g.in_ss = in_ss; g.out = (_Float16*)out; g.partials = partials;
-    g.n = n; g.H = H; g.W = W; g.Cin = cv.cin; g.Cout = cv.cout; g.KH = cv.k; g.KW = cv.k; g.stride = cv.stride; g.pad = cv.pad;
-    g.OH = (H + 2 * cv.pad - cv.k) / cv.stride + 1;
-    g.OW = (W + 2 * cv.pad - cv.k) / cv.stride + 1;
-    g.M = n * g.OH * g.OW;
-    g.wts = R.cur_wts; g.OHWo = g.OH * g.OW;
-    const double invM = 1.0 / (R.cur_wsum * (double)(g.OH * g.OW));    // statistics count: sum of multiplicities x pixels per crop
-    int gridM = (g.M + 127) / 128;
-    g.gridM = gridM;
-    g.gridN = cv.cout == 64 ? 1 : cv.cout / 128;
-    g.out_ss = ss_out; g.idt = (const _Float16*)idt; g.idt_ss = idt_ss; g.zero = (const _Float16*)R.d_zero;
-    if (mode == CONV_MERGE_DS) {
-        const ReidConv& dv = R.convs[ds_idx];
-        g.ds_in = (const _Float16*)ds_in; g.ds_w = (const _Float16*)((const T*)R.d_w + dv.w_off);
-        g.ds_H = dsH; g.ds_W = dsW; g.ds_Cin = dv.cin; g.ds_stride = dv.stride; g.ds_in_ss = ds_in_ss;
-        g.idt_ss = ss_base + dv.ss_off;
-    }
-    const unsigned nblocks = (unsigned)(((gridM + 7) / 8) * 8 * g.gridN);
-    static unsigned long long* ts_buf = nullptr;
-    static int ts_idx = -2, ts_mode = -1;
-    if (ts_idx == -2) { ts_idx = -1; if (const char* e = getenv("BUSCA_CONV_TS")) { ts_idx = atoi(e); if (const char* cm = strchr(e, ',')) ts_mode = atoi(cm + 1); hipMalloc((void**)&ts_buf, 4096 * 8 * 8); } }
-    const bool ts_on = ts_buf != nullptr && idx == ts_idx && (ts_mode < 0 || ts_mode == mode) && nblocks <= 4096;
-    if (ts_on) { hipMemsetAsync(ts_buf, 0, 4096 * 8 * 8, s); g.ts = ts_buf; }
-    // stride-1 3x3 convs with enough tiles to fill the chip: halo-resident kernel (reid_halo.hip.inc)
-    int halo = 0;
-    if (sizeof(T) == 2 && mode == CONV_NORMAL && R.halo && cv.k == 3 && cv.wpk_off != (size_t)-1 && R.d_wpk != nullptr && cv.cin <= 512) {
-        if (W == 32 && H % 4 == 0 && cv.cout == 64 && cv.cin == 64) halo = 1;        // (its kernels take Cin = 64 as a compile-time single chunk)
-        else if (W == 16 && H % 8 == 0 && cv.cout == 128) halo = 2;
-        else if (W == 8 && H == 24 && cv.cout == 256) halo = 3;
-        const int tiles = halo == 3 ? n : g.M / 128;
-        if (halo && tiles * (cv.cout == 256 ? 2 : 1) < R.halo_min_blocks) halo = 0;      // too few workgroups: the K-split-across-waves kernel does better
-    }
-    // large launches of raw-output convs (1x1 / 3x3, stride 1 / 2): pipelined weights-direct kernel (reid_pipe.hip.inc)
-    int pipe = 0;
-    if (sizeof(T) == 2 && mode == CONV_NORMAL && !halo && (cv.k == 1 || cv.k == 3) && cv.cin % 64 == 0 && cv.cin <= 2048 && cv.cout % 128 == 0 &&
-        cv.wkw_off != (size_t)-1 && R.d_wkw != nullptr && R.pipe_min_tiles > 0) {
-        const int nct = cv.cout % 256 == 0 ? 4 : 2;
-        const int t = ((g.M + 127) / 128) * (cv.cout / (64 * nct));
-        // measured IN the 512-crop pass against conv_gemm64_kernel / conv1x1_wd_kernel (profiles/r03_*): the 3x3 convs of layers 3-4
-        // 170-175 -> 152-167 us, layer 4's downsample 140 -> 113, its conv1 127 -> 118 / 70 -> 65-69; layer 3's conv1 (1024 -> 256:
-        // 768 tiles = 1.5 rounds of workgroups) and the 128-channel convs of layer 2 are equal or slower, so they keep the old kernels
-        const bool wins = nct == 4 && (cv.k == 3 || cv.cout >= 512);
-        if (t >= R.pipe_min_tiles && (wins || R.pipe_all)) pipe = nct;
-    }
-    if (pipe) {
-        PipeArgs a{};
-        a.in = (const _Float16*)in; a.in_ss = in_ss; a.wkw = R.d_wkw + cv.wkw_off; a.out = (_Float16*)out; a.partials = partials; a.zero = (const _Float16*)R.d_zero;
-        a.wts = R.cur_wts; a.M = g.M; a.Cin = cv.cin; a.Cout = cv.cout; a.H = H; a.W = W; a.OH = g.OH; a.OW = g.OW; a.stride = cv.stride; a.pad = cv.pad; a.OHWo = g.OHWo;
-        gridM = (g.M + 127) / 128;
-        a.gridN = cv.cout / (64 * pipe);
-        // fewer workgroups than slots (2 per CU): 64-pixel tiles - a workgroup's serial K loop sets the duration of such a launch
-        const bool half_tiles = pipe == 4 && gridM * a.gridN < R.pipe_half_blocks;
-        if (half_tiles) gridM = (g.M + 63) / 64;
-        a.gridM = gridM;
-        const unsigned pb = (unsigned)(((gridM + 7) / 8) * 8 * a.gridN);
-        TimedLaunch tl(c, s);
-#define PIPE_LAUNCH(N_, S_, K_) hipLaunchKernelGGL((conv_pipe_kernel<N_, S_, K_>), dim3(pb), dim3(256), 0, s, a)
-#define PIPE_LAUNCH_H(N_, S_, K_) hipLaunchKernelGGL((conv_pipe_kernel<N_, S_, K_, true, 4>), dim3(pb), dim3(256), 0, s, a)
-        if (half_tiles) {
-            if (cv.k == 3) { if (in_ss) PIPE_LAUNCH_H(4, STG_BN, 3); else PIPE_LAUNCH_H(4, STG_PLAIN, 3); }
-            else { if (in_ss) PIPE_LAUNCH_H(4, STG_BN, 1); else PIPE_LAUNCH_H(4, STG_PLAIN, 1); }
-        } else
-        if (pipe == 4) {
-            if (cv.k == 3) { if (in_ss) PIPE_LAUNCH(4, STG_BN, 3); else PIPE_LAUNCH(4, STG_PLAIN, 3); }
-            else { if (in_ss) PIPE_LAUNCH(4, STG_BN, 1); else PIPE_LAUNCH(4, STG_PLAIN, 1); }
-        } else {
-            if (cv.k == 3) { if (in_ss) PIPE_LAUNCH(2, STG_BN, 3); else PIPE_LAUNCH(2, STG_PLAIN, 3); }
-            else { if (in_ss) PIPE_LAUNCH(2, STG_BN, 1); else PIPE_LAUNCH(2, STG_PLAIN, 1); }
-        }
-#undef PIPE_LAUNCH
-#undef PIPE_LAUNCH_H
-    }
-    // Launches that would leave the LDS-tiled kernel with few workgroups per CU: K split across the waves of a workgroup
-    // (reid_kwave.hip.inc) - smaller tiles, no barrier in the K loop, no f32 round trip through HBM.
-    int kwave = 0, kw_nw = 4, kw_pt = 4;
-    if (!pipe && sizeof(T) == 2 && (mode == CONV_NORMAL || mode == CONV_STATS_ONLY || mode == CONV_MERGE) && cv.cin >= 64 && cv.cin % 64 == 0 && cv.cout % 64 == 0 && cv.k <= 3 &&
-        R.kwave_blocks > 0 && cv.wkw_off != (size_t)-1 && R.d_wkw != nullptr && (double)n * H * W * cv.cin < 2.0e9 && g.M < (1 << 24)) {
-        const int blocks = ((g.M + 127) / 128) * g.gridN;
-        if (blocks < R.kwave_blocks && (!halo || blocks < R.kwave_halo_blocks)) {
-            const int nsteps = cv.k * cv.k * (cv.cin / 64), cb = cv.cout / 64;
-            kw_pt = ((g.M + 63) / 64) * cb >= 256 ? 4 : 2;
-            const int tiles = ((g.M + 16 * kw_pt - 1) / (16 * kw_pt)) * cb;
-            kw_nw = 4;
-            if (tiles * 4 < 1024 && nsteps >= 8) kw_nw = 8;
-            if (kw_pt == 2 && tiles * 8 < 1024 && nsteps >= 16) kw_nw = 16;
-            if (R.kwave_pt == 2 || R.kwave_pt == 4) kw_pt = R.kwave_pt;
-            if (R.kwave_nw == 4 || R.kwave_nw == 8 || (R.kwave_nw == 16 && kw_pt == 2)) kw_nw = R.kwave_nw;
-            // its 64 x 64 tiles read (16 PT + 64) K operand bytes x 2 per tile from L2: beyond a few hundred MB per launch the
-            // L2 becomes the limit (88 crops, layer 4's 3x3: 623 MB, 63 us against 56 us for split-K + reduce)
-            const double mb = (double)tiles * (16 * kw_pt + 64) * nsteps * 64 * 2 / 1e6;
-            const bool thin = blocks >= 192 && nsteps < 8;          // beyond the small-batch regime only the long-K convs (4+ steps per wave)
-            if (mb <= R.kwave_max_mb && !thin) { kwave = 1; halo = 0; }
-        }
-    }
-    // (launched only now: the K-split kernel above may have taken the conv instead - BUSCA_REID_KWAVE_HALO)
-    if (halo) {
-        HaloArgs h{};
-        h.in = (const _Float16*)in; h.wpk = R.d_wpk + cv.wpk_off; h.in_ss = in_ss; h.out = (_Float16*)out; h.partials = partials;
-        h.n = n; h.H = H; h.Cin = cv.cin; h.Cout = cv.cout; h.zero = (const _Float16*)R.d_zero; h.wts = R.cur_wts;
-        h.gridN = cv.cout == 256 ? 2 : 1;
-        // layer 3: a workgroup per image leaves CUs idle below 128 crops -> half images (12 rows, 96 pixels) per workgroup
-        const bool half_img = halo == 3 && n * 2 < R.halo_half_blocks;
-        gridM = halo == 3 ? (half_img ? 2 * n : n) : g.M / 128;
-        // layer 1 at very large batches: 2 x 2 waves on 256-pixel tiles (BUSCA_REID_HALO_WPX / _WPX_MIN, reid_halo.hip.inc)
-        const bool wpx = halo == 1 && R.halo_wpx != 0 && g.M % 256 == 0 && g.M / 256 >= R.halo_wpx_min;
-        if (wpx) gridM = g.M / 256;
-        h.gridM = gridM;
-        const unsigned hb = (unsigned)(((gridM + 7) / 8) * 8 * h.gridN);
-        if (wpx) { hipLaunchKernelGGL((conv3x3_halo_kernel<2, 32, 8, 2>), dim3(hb), dim3(256), 0, s, h); gridM *= 2; }   // two partial-sum rows per tile
-        else if (halo == 1) hipLaunchKernelGGL((conv3x3_halo_kernel<1, 32, 4>), dim3(hb), dim3(256), 0, s, h);
-        else if (halo == 2) hipLaunchKernelGGL((conv3x3_halo_kernel<2, 16, 8>), dim3(hb), dim3(256), 0, s, h);
-        else if (half_img) hipLaunchKernelGGL((conv3x3_halo_kernel<2, 8, 12>), dim3(hb), dim3(256), 0, s, h);
-        else hipLaunchKernelGGL((conv3x3_halo_kernel<2, 8, 24>), dim3(hb), dim3(256), 0, s, h);
-    }
-    if (kwave) {
-        const int bm = 16 * kw_pt;
-        gridM = (g.M + bm - 1) / bm;
-        g.gridM = gridM; g.gridN = cv.cout / 64; g.wkw = R.d_wkw + cv.wkw_off;
-        const unsigned kb = (unsigned)(((gridM + 7) / 8) * 8 * g.gridN);
-        const int nsl = kw_nw / 2 > 4 ? kw_nw / 2 : 4;
-        const size_t tileb = std::max((size_t)nsl * 4 * kw_pt * 1024, (size_t)kw_nw * 16 * kw_pt * 128);
-        const size_t lds = tileb + (size_t)2 * cv.cin * 4 + (size_t)2 * kw_nw * 64 * 4;
-        const size_t lds_max = tileb + (size_t)2 * 2048 * 4 + (size_t)2 * kw_nw * 64 * 4;
-#define KW_LAUNCH(NW_, PT_, DB_)                                                                                                            \
-        do {                                                                                                                                \
-            if (mode == CONV_NORMAL) { int rc = ensure_lds(c, (const void*)conv_kwave_kernel<NW_, PT_, CONV_NORMAL, DB_>, lds_max); if (rc) return rc;  \
-                hipLaunchKernelGGL((conv_kwave_kernel<NW_, PT_, CONV_NORMAL, DB_>), dim3(kb), dim3(NW_ * 64), lds, s, g); }               \
-            else if (mode == CONV_STATS_ONLY) { int rc = ensure_lds(c, (const void*)conv_kwave_kernel<NW_, PT_, CONV_STATS_ONLY, DB_>, lds_max); if (rc) return rc; \
-                hipLaunchKernelGGL((conv_kwave_kernel<NW_, PT_, CONV_STATS_ONLY, DB_>), dim3(kb), dim3(NW_ * 64), lds, s, g); }           \
-            else { int rc = ensure_lds(c, (const void*)conv_kwave_kernel<NW_, PT_, CONV_MERGE, DB_>, lds_max); if (rc) return rc;          \
-                hipLaunchKernelGGL((conv_kwave_kernel<NW_, PT_, CONV_MERGE, DB_>), dim3(kb), dim3(NW_ * 64), lds, s, g); }                \
-        } while (0)
-        if (kw_pt == 4 && kw_nw == 4) KW_LAUNCH(4, 4, 2);
-        else if (kw_pt == 4) KW_LAUNCH(8, 4, 2);
-        else if (kw_nw == 4) KW_LAUNCH(4, 2, 2);
-        else if (kw_nw == 8) KW_LAUNCH(8, 2, 2);
-        else KW_LAUNCH(16, 2, 1);
-#undef KW_LAUNCH
-    }
-    if (halo || kwave || pipe) {
-        // launched above
-    } else {
-        TimedLaunch tl(c, s);
-        if (sizeof(T) == 2) {
-            if (cv.cin == 3) hipLaunchKernelGGL((conv_gemm_kernel<1, true>), dim3(nblocks), dim3(256), 0, s, g);
-            else if (cv.cout == 64) hipLaunchKernelGGL((conv_gemm64_kernel<1, CONV_NORMAL>), dim3(nblocks), dim3(256), 0, s, g);
-            else if (mode == CONV_MERGE_DS) hipLaunchKernelGGL((conv_gemm64_kernel<2, CONV_MERGE_DS>), dim3(nblocks), dim3(256), 0, s, g);
-            else {
-                if (mode == CONV_STATS_ONLY) hipLaunchKernelGGL((conv_gemm64_kernel<2, CONV_STATS_ONLY>), dim3(nblocks), dim3(256), 0, s, g);
-                else if (mode == CONV_MERGE) hipLaunchKernelGGL((conv_gemm64_kernel<2, CONV_MERGE>), dim3(nblocks), dim3(256), 0, s, g);
-                else hipLaunchKernelGGL((conv_gemm64_kernel<2, CONV_NORMAL>), dim3(nblocks), dim3(256), 0, s, g);
-            }
-        } else {
-            if (cv.cin == 3) hipLaunchKernelGGL((conv_f32_kernel<1, true>), dim3(nblocks), dim3(256), 0, s, g);
-            else if (cv.cout == 64) hipLaunchKernelGGL((conv_f32_kernel<1, false>), dim3(nblocks), dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((conv_f32_kernel<2, false>), dim3(nblocks), dim3(256), 0, s, g);
-        }
-    }
-    if (ts_on) {                                        // BUSCA_CONV_TS=<conv index>[,<mode>]: per-workgroup phase stamps of that launch (experiments)
-        hipStreamSynchronize(s);
-        const unsigned nwg = 4096;
-        std::vector<unsigned long long> h((size_t)nwg * 8);
-        hipMemcpy(h.data(), ts_buf, h.size() * 8, hipMemcpyDeviceToHost);
-        double d[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot = 0; int cnt = 0;
-        for (unsigned b = 0; b < nwg; ++b) {
-            const unsigned long long* r = &h[(size_t)b * 8];
-            if (!r[0] || !r[7]) continue;
-            ++cnt; tot += (double)(r[7] - r[0]);
-            for (int k = 1; k <= 7; ++k) if (r[k] && r[k - 1]) d[k] += (double)(r[k] - r[k - 1]);
-        }
-        // stamps: 0 start, 1 after the prologue; third K step: 2 before staging, 3 after the LDS writes, 4 after barrier 1, 5 after
-        // load issue + MFMAs, 6 after barrier 2 (conv_kwave_kernel: 6 = after its K loop); 7 end.  Unit: 100 s_memtime ticks.
-        fprintf(stderr, "[conv_ts] conv %d mode %d M %d Cin %d Cout %d k %d: %d workgroups, mean lifetime %.1f; prologue %.1f | step3: wait+stage %.1f, barrier %.1f, loads+mma %.1f, barrier %.1f | 1->2 %.1f, 6->7 %.1f\n",
-                idx, mode, g.M, cv.cin, cv.cout, cv.k, cnt, tot / cnt / 100.0, d[1] / cnt / 100.0, d[3] / cnt / 100.0, d[4] / cnt / 100.0, d[5] / cnt / 100.0, d[6] / cnt / 100.0,
-                d[2] / cnt / 100.0, d[7] / cnt / 100.0);
-    }
-    *OHo = g.OH; *OWo = g.OW;
-    if (mode == CONV_MERGE || mode == CONV_MERGE_DS) return BUSCA_OK;   // block tail: statistics were final before the launch
-    bn_finalize_launch(s, R, idx, partials, gridM, invM, red, ss_out);
-    *OHo = g.OH; *OWo = g.OW;
-    return BUSCA_OK;
-}
-
-static void ew_preprocess(hipStream_t s, const uint8_t* crops, const uint8_t* zn, size_t npix, _Float16* o) { hipLaunchKernelGGL(reid_preprocess_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, crops, zn, npix, o); }
-static void ew_preprocess(hipStream_t s, const uint8_t* crops, const uint8_t* zn, size_t npix, float* o) { hipLaunchKernelGGL(reid_preprocess_f32_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, crops, zn, npix, o); }
-static void ew_maxpool(hipStream_t s, const _Float16* raw, const float* ss, int n, _Float16* o) { const size_t t = (size_t)n * 96 * 32 * 8; hipLaunchKernelGGL(maxpool_bn_relu_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, raw, ss, n, o); }
-static void ew_maxpool(hipStream_t s, const float* raw, const float* ss, int n, float* o) { const size_t t = (size_t)n * 96 * 32 * 16; hipLaunchKernelGGL(maxpool_bn_relu_f32_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, raw, ss, n, o); }
-static void ew_merge(hipStream_t s, const _Float16* r3, const float* ss3, const _Float16* idt, const float* ssd, size_t npix, int C, _Float16* o) { const size_t t = npix * (C / 8); hipLaunchKernelGGL(block_merge_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, r3, ss3, idt, ssd, npix, C, o); }
-static void ew_merge(hipStream_t s, const float* r3, const float* ss3, const float* idt, const float* ssd, size_t npix, int C, float* o) { const size_t t = npix * (C / 4); hipLaunchKernelGGL(block_merge_f32_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, r3, ss3, idt, ssd, npix, C, o); }
-static void ew_gpool(hipStream_t s, const _Float16* x, int n, int HW, int C, float* o) { const size_t t = (size_t)n * C; hipLaunchKernelGGL(global_maxpool_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, x, n, HW, C, o); }
-static void ew_gpool(hipStream_t s, const float* x, int n, int HW, int C, float* o) { const size_t t = (size_t)n * C; hipLaunchKernelGGL(global_maxpool_f32_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, x, n, HW, C, o); }
-
-template <typename T>
-static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* zero_norm, int32_t n, float* feats, void* stream);
 
 extern "C" int busca_reid_forward_w(busca_ctx* c, const uint8_t* crops, int32_t n, const uint8_t* zero_norm, const float* weights, double weight_sum,
                                     float* feats, void* stream) {
     if (!c) return BUSCA_EINVAL;
     if (!c->reid->loaded) return fail(c, BUSCA_ENOWEIGHTS, "busca_reid_forward before busca_reid_load_weights");
     if (weights != nullptr && !(weight_sum >= 1.0)) return fail(c, BUSCA_EINVAL, "busca_reid_forward_w: weight_sum must be the (>= 1) sum of the multiplicities");
-    ReidState& R = *c->reid;
-    R.cur_wts = weights; R.cur_wsum = weights != nullptr ? weight_sum : (double)n;
-    const int rc = R.prec != BUSCA_PREC_F16 ? reid_forward_impl<float>(c, crops, zero_norm, n, feats, stream)
-                                            : reid_forward_impl<_Float16>(c, crops, zero_norm, n, feats, stream);
-    R.cur_wts = nullptr;
-    return rc;
+    switch (c->reid->prec) {
+        case BUSCA_PREC_F16: return reid_forward_impl<ReidF16>(c, crops, zero_norm, n, weights, weight_sum, feats, stream);
+        case BUSCA_PREC_F16X3: return reid_forward_impl<ReidX3>(c, crops, zero_norm, n, weights, weight_sum, feats, stream);
+        default: return reid_forward_impl<ReidF32>(c, crops, zero_norm, n, weights, weight_sum, feats, stream);
+    }
 }
 
 extern "C" int busca_reid_forward_ex(busca_ctx* c, const uint8_t* crops, int32_t n, const uint8_t* zero_norm, float* feats, void* stream) {
@@ -787,25 +40,6 @@ extern "C" int busca_reid_forward(busca_ctx* c, const uint8_t* crops, int32_t n,
     return busca_reid_forward_ex(c, crops, n, nullptr, feats, stream);
 }
 
-// The workspace of the stream that calls: found, or claimed from the pool of 4, grown when the batch is larger than any before
-// (device synchronisation + hipMalloc - busca_reid_reserve moves that out of the forward).
-static int reid_ws_acquire(busca_ctx* c, int n, void* stream, size_t es, ReidState::WS** out) {
-    ReidState& R = *c->reid;
-    ReidState::WS* w = nullptr;
-    for (auto& e : R.ws) if (e.ptr && e.stream == stream) { w = &e; break; }
-    if (!w) for (auto& e : R.ws) if (!e.ptr) { w = &e; w->stream = stream; break; }
-    if (!w) { HIP_TRY(c, hipDeviceSynchronize()); w = &R.ws[0]; w->stream = stream; }   // pool exhausted: recycle slot 0
-    if (w->n < n) {
-        if (w->ptr) { HIP_TRY(c, hipDeviceSynchronize()); HIP_TRY(c, hipFree(w->ptr)); w->ptr = nullptr; w->n = 0; }
-        const size_t bytes = reid_ws::bytes(n, es);
-        if (hipMalloc(&w->ptr, bytes) != hipSuccess) return fail(c, BUSCA_ENOMEM, "cannot allocate %zu bytes of ReID workspace for %d crops", bytes, n);
-        w->bytes = bytes; w->n = n;
-        HIP_TRY(c, hipMemset(w->ptr, 0, reid_ws::TICKET_BYTES));
-    }
-    *out = w;
-    return BUSCA_OK;
-}
-
 extern "C" int busca_reid_reserve(busca_ctx* c, int32_t n, void* stream) {
     if (!c) return BUSCA_EINVAL;
     if (!c->reid->loaded) return fail(c, BUSCA_ENOWEIGHTS, "busca_reid_reserve before busca_reid_load_weights");
@@ -813,226 +47,4 @@ extern "C" int busca_reid_reserve(busca_ctx* c, int32_t n, void* stream) {
     HIP_TRY(c, hipSetDevice(c->device));
     ReidState::WS* w = nullptr;
     return reid_ws_acquire(c, n, stream, c->reid->prec != BUSCA_PREC_F16 ? 4 : 2, &w);
-}
-
-template <typename T>
-static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* zero_norm, int32_t n, float* feats, void* stream) {
-    ReidState& R = *c->reid;
-    if (n < 0) return fail(c, BUSCA_EINVAL, "negative batch");
-    if (n == 0) return BUSCA_OK;
-    if (!crops || !feats) return fail(c, BUSCA_EINVAL, "null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    ReidState::WS* w = nullptr;
-    { int rc = reid_ws_acquire(c, n, stream, sizeof(T), &w); if (rc) return rc; }
-    // carve
-    char* p = (char*)w->ptr;
-    auto take = [&](size_t bytes) { char* q = p; p += (bytes + 255) & ~(size_t)255; return q; };
-    const size_t nn = n;
-    R.cur_tickets = (int*)take(reid_ws::TICKET_BYTES);   // first block: its offset does not depend on n
-    // every arrival counter is zero before the pass starts (a memset node ahead of the launches: a pass that was cut short - an error,
-    // a cancelled stream - must not leave a ticket behind for the next one; the last arrivers also put theirs back to zero)
-    float* ssb = (float*)take((size_t)2 * 26560 * 4);      // (scale, shift) of every BN channel of THIS batch; right behind the tickets: ONE memset node zeroes both (the
-                                                           // split-fp16 flavour's end-of-pass scan for non-finite entries must never read a stale word)
-    HIP_TRY(c, hipMemsetAsync(R.cur_tickets, 0, reid_ws::TICKET_BYTES + (size_t)2 * 26560 * 4, s));
-    T* in4 = (T*)take(nn * reid_ws::IN4 * sizeof(T));
-    T* stem = (T*)take(nn * reid_ws::STEM * sizeof(T));
-    T* x0 = (T*)take(nn * reid_ws::X0 * sizeof(T));
-    T* r1 = (T*)take(nn * reid_ws::R1 * sizeof(T));
-    T* r2 = (T*)take(nn * reid_ws::R2 * sizeof(T));
-    T* r3 = (T*)take(nn * reid_ws::R3 * sizeof(T));
-    T* rd = (T*)take(nn * reid_ws::RD * sizeof(T));
-    T* xa = (T*)take(nn * reid_ws::XA * sizeof(T));
-    T* xb = (T*)take(nn * reid_ws::XB * sizeof(T));
-    float* partials = (float*)take((nn * reid_ws::PART_FLOATS + 2 * 2 * 2048) * 4);
-    float* pool = (float*)take(nn * 2048 * 4);
-    double* red = (double*)take((size_t)BN_SLICES * 2 * 2048 * 8);
-    float* fc7 = (float*)take(nn * 512 * 4);
-    float* gpart = nullptr; double* gG = nullptr;
-    if (sizeof(T) == 2) { gpart = (float*)take(reid_ws::GRAM_PART_FLOATS * 4); gG = (double*)take(reid_ws::GRAM_G_DOUBLES * 8); }
-    double* x3part = nullptr; double* x3G = nullptr;
-    if (sizeof(T) == 4) { x3part = (double*)take(reid_ws::X3_GRAM_PART_DOUBLES * 8); x3G = (double*)take(reid_ws::X3_GRAM_G_DOUBLES * 8); }
-
-    const size_t npix_in = nn * 384 * 128;
-    R.cur_pool_p = nullptr; R.cur_pool_q = nullptr;
-    int H = 384, W = 128, OH, OW, ci = 0;
-    const float* x0_ss = nullptr;                         // (scale, shift) the consumers of x0 must apply, or NULL when x0 holds final values
-    if (sizeof(T) == 2 && R.halo) {
-        // u8 crops -> raw stem output in one kernel (normalisation folded into the halo staging; reid_halo.hip.inc)
-        const ReidConv& cv = R.convs[0];
-        StemArgs a{};
-        a.crops = crops; a.zero_norm = zero_norm; a.w = R.d_wpk + R.stem_wpk_off; a.lut = R.d_wpk + R.stem_lut_off; a.out = (_Float16*)stem; a.partials = partials; a.n = n; a.gridM = n * 48;
-        a.wts = R.cur_wts;
-        const double inv_stem = 1.0 / (R.cur_wsum * 192.0 * 64.0);
-        a.out = (_Float16*)x0; a.negmask = R.stem_negmask;      // raw stem output, already max-pooled (min where gamma < 0): see stem_pool_kernel
-        hipLaunchKernelGGL((stem_pool_kernel<2>), dim3(a.gridM), dim3(256), 0, s, a);
-        float* ss_out = ssb + cv.ss_off;
-        bn_finalize_launch(s, R, 0, partials, a.gridM, inv_stem, red, ss_out);
-        x0_ss = ss_out;                                   // x0 is RAW: its consumers apply the stem's BatchNorm + ReLU while staging
-    } else {
-        const bool stem_u8 = sizeof(T) == 4 && R.prec == BUSCA_PREC_F16X3 && R.x3_stem_halo && R.x3_stem_u8 && R.d_x3_lut != nullptr;
-        const bool stem_pool = sizeof(T) == 4 && R.prec == BUSCA_PREC_F16X3 && R.x3_stem_halo && R.x3_stem_pool;
-        if (stem_u8) { R.cur_crops = crops; R.cur_zn = zero_norm; }     // the stem fills its input halo from the bytes (no normalised copy of the batch)
-        else ew_preprocess(s, crops, zero_norm, npix_in, in4);
-        if (stem_pool) {
-            // the stem writes the max pool of its RAW output (x sign(gamma)) in two parts - x0 = P, `stem` = Q - and layer 1's first conv1 / downsample conv
-            // stage relu(bn(max(P, Q above))): the full-resolution raw map (1.6 GB per 512 crops) and the pooling pass are gone
-            R.cur_pool_p = (const float*)x0; R.cur_pool_q = (float*)stem;
-            int rc = reid_conv_launch(c, s, R, ci, in4, nullptr, n, H, W, x0, partials, red, ssb, &OH, &OW);
-            R.cur_crops = nullptr; R.cur_zn = nullptr;
-            if (rc) { R.cur_pool_p = nullptr; R.cur_pool_q = nullptr; return rc; }
-            x0_ss = ssb + R.convs[0].ss_off;
-        } else {
-        { int rc = reid_conv_launch(c, s, R, ci, in4, nullptr, n, H, W, stem, partials, red, ssb, &OH, &OW); R.cur_crops = nullptr; R.cur_zn = nullptr; if (rc) return rc; }            // 192 x 64
-        ew_maxpool(s, (const T*)stem, (const float*)(ssb + R.convs[0].ss_off), n, x0);
-        }
-    }
-    ci = 1; H = 96; W = 32;
-    T* cur = x0; T* nxt = xa;
-    const int nblk[4] = {3, 4, 6, 3};
-    bool conv1_done = false;
-    // split-fp16 flavour, layers whose tail is not a conv3 epilogue: the tail relu(bn3(raw3) + identity) is DEFERRED into the next
-    // bottleneck's conv1, which forms it while staging its operand and writes it out as the next identity (no block_merge pass)
-    const T* pend_raw = nullptr; const float* pend_ss = nullptr; const T* pend_idt = nullptr; const float* pend_idt_ss = nullptr; T* pend_out = nullptr;
-    for (int li = 0; li < 4; ++li)
-        for (int b = 0; b < nblk[li]; ++b) {
-            int h1, w1, h2, w2, h3, w3, hd, wd;
-            const int i1 = ci, i2 = ci + 1, i3 = ci + 2, id = ci + 3;
-            const float* cur_ss = (li == 0 && b == 0) ? x0_ss : nullptr;      // only the first bottleneck reads the (raw, pooled) stem tensor
-            if (conv1_done) { h1 = H; w1 = W; conv1_done = false; }            // produced by the previous block's fused tail
-            else if (pend_out != nullptr) {
-                int rc = reid_conv_launch(c, s, R, i1, pend_raw, pend_ss, n, H, W, r1, partials, red, ssb, &h1, &w1, CONV_NORMAL, (const T*)nullptr, nullptr, -1, (const T*)nullptr, 0, 0, nullptr,
-                                          pend_idt, pend_idt_ss, pend_out);
-                if (rc) return rc;
-                pend_out = nullptr;                      // cur (== the old pend_out) now holds the previous block's output
-            }
-            else { int rc = reid_conv_launch(c, s, R, i1, cur, cur_ss, n, H, W, r1, partials, red, ssb, &h1, &w1); if (rc) return rc; }
-            { int rc = reid_conv_launch(c, s, R, i2, r1, ssb + R.convs[i1].ss_off, n, h1, w1, r2, partials, red, ssb, &h2, &w2); if (rc) return rc; }
-            const T* idt = cur; const float* ssd = nullptr;
-            const int hh2 = (h1 + 2 - 3) / R.convs[i2].stride + 1, ww2 = (w1 + 2 - 3) / R.convs[i2].stride + 1;   // == h2, w2
-            const bool gram = reid_use_gram(R, li, n * hh2 * ww2, hh2 * ww2);
-            const bool fuse_ds = gram && R.gram_mode != 2 && ((R.fuse_ds_layers >> li) & 1);
-            if (b == 0 && !fuse_ds) {
-                { int rc = reid_conv_launch(c, s, R, id, cur, cur_ss, n, H, W, rd, partials, red, ssb, &hd, &wd); if (rc) return rc; }
-                idt = rd; ssd = ssb + R.convs[id].ss_off;
-            }
-            const bool fuse_c1 = (li == 0 || (li <= R.fuse_c1_layers - 1 && b > 0)) && R.halo && R.fuse_c1;
-            auto launch_tail_c1 = [&](bool ds) {
-                // layer-1 tail + the NEXT bottleneck's conv1 in one kernel (reid_halo.hip.inc): that conv never re-reads this output
-                const int inext = ci + (b == 0 ? 4 : 3);                      // conv1 of the next block (layer 1 b+1, or layer 2 b0)
-                const ReidConv& c3 = R.convs[i3]; const ReidConv& cn = R.convs[inext];
-                TailC1Args ta{};
-                ta.in = (const _Float16*)r2; ta.in_ss = ssb + R.convs[i2].ss_off; ta.w3 = (const _Float16*)R.d_w + c3.w_off;
-                ta.out_ss = ssb + c3.ss_off; ta.idt = (const _Float16*)cur; ta.out = (_Float16*)nxt;
-                if (ds) { ta.ds_in = (const _Float16*)cur; ta.ds_w = (const _Float16*)R.d_w + R.convs[id].w_off; ta.idt_ss = ssb + R.convs[id].ss_off; ta.ds_in_ss = cur_ss; }
-                ta.w1pk = R.d_wpk + cn.wpk_off; ta.out2 = (_Float16*)r1; ta.partials2 = partials; ta.M = n * h2 * w2;
-                ta.wts = R.cur_wts; ta.OHW = h2 * w2;
-                const int gm = ta.M / (li == 2 ? 64 : 128);
-#ifdef BUSCA_CONV_PROBE
-                static unsigned long long* tts = nullptr;              // BUSCA_TAIL_TS=<index of conv3>: phase stamps of that fused tail
-                static const int tts_idx = getenv("BUSCA_TAIL_TS") ? atoi(getenv("BUSCA_TAIL_TS")) : -1;
-                const bool tts_on = tts_idx == i3;
-                if (tts_on) { if (!tts) hipMalloc((void**)&tts, 4096 * 8 * 8); hipMemsetAsync(tts, 0, 4096 * 8 * 8, s); ta.ts = tts; }
-#endif
-                if (ds) hipLaunchKernelGGL((tail_conv1_kernel<128, 64, 256, 64, true>), dim3(gm), dim3(256), 0, s, ta);
-                else if (li == 0 && cn.cout == 64) hipLaunchKernelGGL((tail_conv1_kernel<128, 64, 256, 64, false>), dim3(gm), dim3(256), 0, s, ta);
-                else if (li == 0) hipLaunchKernelGGL((tail_conv1_kernel<128, 64, 256, 128, false>), dim3(gm), dim3(256), 0, s, ta);
-                else if (li == 1 && cn.cout == 128) hipLaunchKernelGGL((tail_conv1_kernel<128, 128, 512, 128, false>), dim3(gm), dim3(512), 0, s, ta);
-                else if (li == 1) hipLaunchKernelGGL((tail_conv1_kernel<128, 128, 512, 256, false>), dim3(gm), dim3(512), 0, s, ta);
-                else if (cn.cout == 256) hipLaunchKernelGGL((tail_conv1_kernel<64, 256, 1024, 256, false>), dim3(gm), dim3(1024), 0, s, ta);
-                else hipLaunchKernelGGL((tail_conv1_kernel<64, 256, 1024, 512, false>), dim3(gm), dim3(1024), 0, s, ta);
-#ifdef BUSCA_CONV_PROBE
-                if (tts_on) {
-                    hipStreamSynchronize(s);
-                    std::vector<unsigned long long> h((size_t)4096 * 8);
-                    hipMemcpy(h.data(), tts, h.size() * 8, hipMemcpyDeviceToHost);
-                    double d[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot = 0; int cnt = 0;
-                    for (int b = 0; b < 4096 && b < gm; ++b) {
-                        const unsigned long long* r = &h[(size_t)b * 8];
-                        if (!r[0] || !r[7]) continue;
-                        ++cnt; tot += (double)(r[7] - r[0]);
-                        const int seq[7] = {0, 1, 2, 3, 4, 5, 7};
-                        for (int k = 1; k < 7; ++k) d[k] += (double)(r[seq[k]] - r[seq[k - 1]]);
-                    }
-                    fprintf(stderr, "[tail_ts] conv3 %d (%d -> %d, next conv1 -> %d) M %d: %d workgroups, mean lifetime %.1f | load+stage A %.1f, conv3 MFMAs %.1f, raw tile + epilogue %.1f, barrier %.1f, conv1 MFMAs %.1f, stats + stores %.1f   (100 s_memtime ticks)\n",
-                            i3, c3.cin, c3.cout, cn.cout, ta.M, cnt, tot / cnt / 100, d[1] / cnt / 100, d[2] / cnt / 100, d[3] / cnt / 100, d[4] / cnt / 100, d[5] / cnt / 100, d[6] / cnt / 100);
-                }
-#endif
-                bn_finalize_launch(s, R, inext, partials, gm, 1.0 / (R.cur_wsum * (double)(h2 * w2)), red, ssb + cn.ss_off);
-                h3 = h2; w3 = w2;
-                conv1_done = true;
-            };
-            if (sizeof(T) == 2 && gram) {
-                // BN3 (and the downsample's BN) statistics from Gram matrices of the 4x narrower inputs; then ONE conv3 pass
-                // whose epilogue is the block tail, with the downsample conv accumulated by the same workgroup
-                { int rc = reid_gram_stats(c, s, R, i3, (const _Float16*)r2, ssb + R.convs[i2].ss_off, n, h2, w2, gpart, gG, ssb); if (rc) return rc; }
-                if (b == 0 && fuse_ds && fuse_c1) {
-                    { int rc = reid_gram_stats(c, s, R, id, (const _Float16*)cur, cur_ss, n, H, W, gpart, gG, ssb); if (rc) return rc; }
-                    launch_tail_c1(true);
-                } else if (b == 0 && fuse_ds) {
-                    { int rc = reid_gram_stats(c, s, R, id, (const _Float16*)cur, cur_ss, n, H, W, gpart, gG, ssb); if (rc) return rc; }
-                    { int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, nxt, partials, red, ssb, &h3, &w3, CONV_MERGE_DS, (const T*)nullptr, nullptr, id, cur, H, W, cur_ss); if (rc) return rc; }
-                } else if (fuse_c1 && b > 0) {
-                    launch_tail_c1(false);
-                } else
-                    { int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, nxt, partials, red, ssb, &h3, &w3, CONV_MERGE, idt, ssd); if (rc) return rc; }
-            } else if (sizeof(T) == 2) {
-                // conv3 twice: statistics-only pass, then a pass whose epilogue is the block tail (no raw3 tensor)
-                { int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, r3, partials, red, ssb, &h3, &w3, CONV_STATS_ONLY); if (rc) return rc; }
-                if (fuse_c1 && b > 0 && R.fuse_c1_small && (n * h2 * w2) % (li == 2 ? 64 : 128) == 0)
-                    launch_tail_c1(false);       // the tail also runs the next bottleneck's conv1 (statistics came from the pass above)
-                else
-                { int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, nxt, partials, red, ssb, &h3, &w3, CONV_MERGE, idt, ssd); if (rc) return rc; }
-            } else if (R.prec == BUSCA_PREC_F16X3 && ((R.x3_merge_layers >> li) & 1)) {
-                // split-fp16 flavour: BN3 statistics first - from the Gram matrix of conv3's 4x narrower input where that is built (64 / 128 channels, tiles inside
-                // one crop), else a statistics-only pass of conv3 - then a pass whose epilogue is the block tail (the 4x wider raw tensor is never written or read back)
-                const int c3in = R.convs[i3].cin;
-                if (R.x3_gram && (c3in == 64 || c3in == 128) && (h2 * w2) % 128 == 0 && (size_t)n * h2 * w2 * c3in >= (size_t)R.x3_gram_min && R.convs[i3].cout % QF_CPB == 0) {
-                    int rc = c3in == 64 ? x3_gram_stats_c<64>(c, s, R, i3, (const float*)r2, ssb + R.convs[i2].ss_off, n, h2 * w2, x3part, x3G, ssb + R.convs[i3].ss_off)
-                                        : x3_gram_stats_c<128>(c, s, R, i3, (const float*)r2, ssb + R.convs[i2].ss_off, n, h2 * w2, x3part, x3G, ssb + R.convs[i3].ss_off);
-                    if (rc) return rc;
-                } else
-                { int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, r3, partials, red, ssb, &h3, &w3, CONV_STATS_ONLY); if (rc) return rc; }
-                // layer 1: the tail pass also runs the next bottleneck's conv1 (256 -> 64, or layer 2's 256 -> 128) on the tile it holds - that conv never re-reads
-                // the 4x wide block output (1.6 GB per 512 crops)
-                const int inext = ci + (b == 0 ? 4 : 3);
-                const bool c1_in_tail = R.x3_fuse_c1 && R.convs[i3].cout == 256 && inext < (int)R.convs.size() && R.convs[inext].k == 1 && R.convs[inext].stride == 1 &&
-                                        R.convs[inext].cin == 256 && (R.convs[inext].cout == 64 || R.convs[inext].cout == 128) &&
-                                        (size_t)n * h2 * w2 * 256 >= (size_t)R.x3_fuse_c1_min;
-                if (c1_in_tail) {
-                    int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, nxt, partials, red, ssb, &h3, &w3, CONV_MERGE, idt, ssd, -1, (const T*)nullptr, 0, 0, nullptr,
-                                              (const T*)nullptr, nullptr, (T*)nullptr, inext, r1);
-                    if (rc) return rc;
-                    conv1_done = true;
-                } else
-                { int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, nxt, partials, red, ssb, &h3, &w3, CONV_MERGE, idt, ssd); if (rc) return rc; }
-            } else {
-                { int rc = reid_conv_launch(c, s, R, i3, r2, ssb + R.convs[i2].ss_off, n, h2, w2, r3, partials, red, ssb, &h3, &w3); if (rc) return rc; }
-                const int C = R.convs[i3].cout;
-                const size_t npix = nn * h3 * w3;
-                const bool last = li == 3 && b == nblk[3] - 1;
-                const int inext = ci + (b == 0 ? 4 : 3);
-                if (R.prec == BUSCA_PREC_F16X3 && R.x3_merge_in && !last && npix * C >= (size_t)R.x3_merge_in_min && R.convs[inext].k == 1 && R.convs[inext].stride == 1 && R.convs[inext].cout % 256 == 0) {
-                    pend_raw = r3; pend_ss = ssb + R.convs[i3].ss_off; pend_idt = idt; pend_idt_ss = ssd; pend_out = nxt;
-                } else
-                ew_merge(s, (const T*)r3, (const float*)(ssb + R.convs[i3].ss_off), idt, ssd, npix, C, nxt);
-            }
-            ci += (b == 0) ? 4 : 3;
-            H = h3; W = w3;
-            cur = nxt; nxt = (cur == xa) ? xb : xa;
-        }
-    {
-        R.cur_pool_p = nullptr; R.cur_pool_q = nullptr;
-        ew_gpool(s, (const T*)cur, n, H * W, 2048, pool);
-        (void)fc7;
-        if (n >= 128)
-            hipLaunchKernelGGL((reid_tail_gemv_kernel<8>), dim3((n + 7) / 8, 8), dim3(256), 0, s, (const float*)pool, (const float*)(R.d_f + R.red_w_off),
-                               (const float*)(R.d_f + R.red_b_off), feats, n);
-        else
-            hipLaunchKernelGGL((reid_tail_gemv_kernel<1>), dim3(n, 8), dim3(256), 0, s, (const float*)pool, (const float*)(R.d_f + R.red_w_off),
-                               (const float*)(R.d_f + R.red_b_off), feats, n);
-        // (split-fp16 flavour: the same launch scans this pass's BatchNorm (scale, shift) table and the features for non-finite values -> "reid_status")
-        hipLaunchKernelGGL(reid_l2norm_kernel, dim3(n), dim3(256), 0, s, feats, (const float*)ssb, 2 * 26560, R.prec == BUSCA_PREC_F16X3 ? R.xerr_dev : (int*)nullptr);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return BUSCA_OK;
 }

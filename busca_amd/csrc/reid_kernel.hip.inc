@@ -819,88 +819,3 @@ __global__ void __launch_bounds__(256) reid_l2norm_kernel(float* __restrict__ fe
         if (bad) *flag = 2;
     }
 }
-
-// ---- host-side state ----------------------------------------------------------------------------------------------
-struct ReidConv { int cout, cin, k, stride, pad; size_t w_off, g_off, b_off, ss_off; size_t wpk_off = (size_t)-1; size_t wkw_off = (size_t)-1;
-                  size_t wx3_off = (size_t)-1, inv_off = 0; };   // F16X3: hi / lo fragment-ordered weights (halves into d_wx3), per-channel descale (floats into d_f)   // offsets into dev arrays; wpk: fragment-packed copy (reid_halo.hip.inc)
-
-struct ReidState {
-    bool loaded = false;
-    int prec = BUSCA_PREC_F16;        // element type of activations / conv weights
-    std::vector<ReidConv> convs;      // forward order (53); w_off in ELEMENTS
-    void* d_w = nullptr;              // all packed conv weights (fp16 or f32)
-    _Float16* d_wpk = nullptr;        // fragment-ordered copies of the stride-1 3x3 and stem weights + stem byte table (fp16 flavour)
-    _Float16* d_wkw = nullptr;        // fragment-ordered copies of every non-stem conv, half-step major (reid_kwave.hip.inc)
-    _Float16* d_wx3 = nullptr;        // F16X3: hi / lo fragment-ordered, per-channel pre-scaled copies of every conv (reid_x3.hip.inc)
-    int x3_ptail_min = 128;           // F16X3: the fused tails of layers 1-2 run as PERSISTENT workgroups (reid_x3p.hip.inc) from this many (128-pixel tile, 256-channel block)
-                                      // work items up (measured: 22 crops 2.212 -> 2.198 ms, 40 crops 2.595 -> 2.558 against 512); 0 = never (BUSCA_REID_X3_PTAIL)
-    int num_cu = 256;                 // compute units of the device (persistent launches: one workgroup per CU)
-    int x3_half_blocks = -1;          // F16X3: 64-pixel tiles while 128-pixel tiles would give fewer workgroups than this (BUSCA_REID_X3_HALF; 0 = never; -1 = by the number of
-                                      // workgroup rounds, see reid_x3_conv)
-    int x3_gram_min = 4 << 20;        // ... and only from this many input elements (pixels x channels) up: below, the statistics-only pass is faster (BUSCA_REID_X3_GRAM_MIN)
-    int x3_merge_in_min = 8 << 20;    // ... from this many block-output elements up (below, the separate pass is as fast; BUSCA_REID_X3_MERGE_IN_MIN)
-    int x3_narrow3 = 200;             // F16X3: 3x3 convs with fewer 64-pixel x 256-channel workgroups than this run on 64 x 128 four-wave workgroups (BUSCA_REID_X3_NARROW3; 0 = never; 32 crops 2.60 -> 2.47 ms, equal at 88, slower from ~100)
-    bool x3_stem_halo = true;         // F16X3: the stem stages its input rows once per tile as an LDS halo (STEMH; BUSCA_REID_X3_STEM_HALO=0: tap by tap)
-    int x3_row3 = 1;                  // F16X3: stride-1 3x3 convs of layers 1-2 stage once per kernel row (ROW3; BUSCA_REID_X3_ROW3=0: once per tap)
-    bool x3_fuse_c1 = true;           // F16X3: layer 1's fused tails also run the next bottleneck's conv1 (X3_MERGE_C1; BUSCA_REID_X3_FUSE_C1=0)
-    int x3_fuse_c1_min = 0;           // ... from this many block-output elements up (BUSCA_REID_X3_FUSE_C1_MIN)
-    bool x3_merge_in = true;          // F16X3: a block tail that is not a conv3 epilogue is formed by the NEXT conv1 while it stages (BUSCA_REID_X3_MERGE_IN=0: block_merge pass)
-    bool x3_gram = true;              // F16X3: BN3 statistics of layers 1-2 from the Gram matrix of conv3's input (x3_gram_kernel) instead of a statistics-only conv pass (BUSCA_REID_X3_GRAM=0)
-    int x3_merge_layers = 3;          // F16X3: bit l = layer l+1 runs conv3 as statistics pass + fused-tail pass (no raw conv3 tensor) instead of raw output + merge pass
-    size_t stem_wpk_off = 0, stem_lut_off = 0;
-    int direct_rows = 512;            // statistics of up to this many tiles are reduced + finalised by ONE launch (BUSCA_REID_DIRECT_ROWS)
-    int fuse_ds_layers = 3;           // bit l: the first block of layer l+1 accumulates its downsample conv inside the fused tail (Gram statistics for its BatchNorm);
-                                      // 0 bits: separate raw-output conv.  Layer 3 is NOT fused since round 3: its downsample as a conv_pipe_kernel launch (131 us) + a plain
-                                      // fused-tail pass replace the 170 us Gram chain of the branch and the two-accumulator tail: 512 crops 8.30 -> 8.14 ms (BUSCA_REID_FUSE_DS_LAYERS)
-    bool two_launch_stats = false;    // BUSCA_REID_STATS2=1: separate reduce + finalise launches beyond direct_rows (A/B; default: one launch, last arriver finalises)
-    bool fuse_c1 = true;              // BUSCA_REID_FUSE_C1=0: tails without the fused next conv1 (A/B testing); 1/2/3 = through that layer
-    int fuse_c1_layers = 2;           // layer 3 (64-pixel tiles, 16 waves) measured slower: 9.76 -> 10.25 ms at 512 crops; opt-in with =3
-    bool fuse_c1_small = true;        // fused tail + next conv1 also behind a statistics-only pass (small batches, no Gram); BUSCA_REID_FUSE_C1_SMALL=0 off
-    bool halo = true;                 // BUSCA_REID_HALO=0 disables the halo-resident 3x3 kernel (A/B testing)
-    int halo_min_blocks = 128;        // halo 3x3 kernel from this many workgroups on (BUSCA_REID_HALO_MIN; below: generic / split-K)
-    int halo_wpx = 1;                 // layer 1's 3x3: 2 x 2-wave halo kernel on 256-pixel tiles (BUSCA_REID_HALO_WPX=0: never)
-    int halo_wpx_min = 5120;          // ... from this many 256-pixel tiles on (427 crops; BUSCA_REID_HALO_WPX_MIN)
-    int halo_half_blocks = 384;       // layer-3 halo kernel on half images below this many full-image workgroups (BUSCA_REID_HALO_HALF)
-    int gram_min_pixels = 65536;      // Gram statistics from this many output pixels on (BUSCA_REID_GRAM_MIN)
-    int pipe_min_tiles = 192;         // conv_pipe_kernel (reid_pipe.hip.inc) for raw-output convs from this many 128-pixel x 256-channel tiles on (BUSCA_REID_PIPE_MIN; 0 = never)
-    int pipe_half_blocks = 448;       // ... on 64-pixel tiles while 128-pixel tiles would give fewer workgroups than this (BUSCA_REID_PIPE_HALF; 0 = never)
-    bool pipe_all = false;            // ... for every eligible conv instead of the shapes where it measured faster (BUSCA_REID_PIPE_ALL; tests)
-                                      // the default: measured equal to the tiled kernel, 83 vs 85 us per layer-3/4 conv1 at 512 crops)
-    int* cur_tickets = nullptr;       // [conv][64-channel column] arrival counters of bn_reduce_finalize_kernel (carved from the workspace of the running forward)
-    int kwave_blocks = 288;           // conv_kwave_kernel instead of the LDS-tiled kernel below this many 128x128 tiles (BUSCA_REID_KWAVE_BLOCKS; 0 = never)
-    int kwave_halo_blocks = 0;        // ... also instead of the halo 3x3 kernel below this many tiles (BUSCA_REID_KWAVE_HALO)
-    double kwave_max_mb = 600.0;       // ... and only while its operand traffic per launch stays below this many MB (BUSCA_REID_KWAVE_MB)
-    int kwave_nw = 0, kwave_pt = 0;   // forced waves per workgroup / pixel fragments per tile (experiments; 0 = automatic)
-    float* d_f = nullptr;             // gamma/beta for every BN, red weight^T [2048][512], red bias
-    float* d_ss = nullptr;            // scale/shift per BN channel [sum C][2]
-    size_t red_w_off = 0, red_b_off = 0;
-    unsigned long long stem_negmask = 0;   // bit c: the stem BatchNorm's gamma of channel c is negative (stem_pool_kernel pools it with min)
-    void* d_zero = nullptr;           // 256 zero bytes: the load target of padded / out-of-range operand pieces
-    int gram_mode = -1;               // BUSCA_REID_GRAM: -1 auto (large batches), 0 never, 1 always (see reid_gram.hip.inc)
-    const uint8_t* cur_crops = nullptr; const uint8_t* cur_zn = nullptr;   // F16X3 stem with byte input: the crops / padding flags of the forward that is being enqueued
-    unsigned* d_x3_lut = nullptr;     // F16X3: [3][256] pre-split normalised values of the stem's byte input (reid_x3.hip.inc STEMH)
-    const float* cur_pool_p = nullptr; float* cur_pool_q = nullptr;      // F16X3: the pooled stem parts of the forward that is being enqueued (X3_POOL / X3_POOLIN)
-    bool x3_stem_pool = true;         // F16X3: the stem writes the max pool of its raw output instead of the raw map (BUSCA_REID_X3_STEM_POOL=0: raw map + pooling pass)
-    bool x3_stem_u8 = true;           // F16X3: the stem reads the u8 crops itself (BUSCA_REID_X3_STEM_U8=0: through the normalised float copy)
-    int* xerr = nullptr; int* xerr_dev = nullptr;    // F16X3: status word in host-mapped memory ("reid_status": 2 = a staged operand left the fp16 range in a forward since it was last cleared)
-    const float* cur_wts = nullptr;   // per-crop multiplicities of the forward that is being enqueued (busca_reid_forward_w), else NULL
-    double cur_wsum = 0.0;            // their sum (= n without weights)
-    // workspaces: one per stream that has called busca_reid_forward (the two BN batches of a step may run
-    // concurrently on two streams); reused, grown on demand
-    struct WS { void* stream = nullptr; void* ptr = nullptr; size_t bytes = 0; int n = 0; };
-    WS ws[4];
-};
-
-static void reid_free(ReidState& r) {
-    if (r.d_w) hipFree(r.d_w);
-    if (r.d_wpk) hipFree(r.d_wpk);
-    if (r.d_wkw) hipFree(r.d_wkw);
-    if (r.d_wx3) hipFree(r.d_wx3);
-    if (r.d_x3_lut) { hipFree(r.d_x3_lut); r.d_x3_lut = nullptr; }
-    if (r.d_f) hipFree(r.d_f);
-    if (r.d_ss) hipFree(r.d_ss);
-    if (r.d_zero) hipFree(r.d_zero);
-    for (auto& w : r.ws) if (w.ptr) hipFree(w.ptr);
-    if (r.xerr) hipHostFree(r.xerr);
-    r = ReidState();
-}

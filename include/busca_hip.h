@@ -54,7 +54,7 @@ const char* busca_last_error(const busca_ctx* ctx);
 int busca_version(void);
 /* The compiler flags this library was built with (busca_amd/build.py passes them in; bench.py records the string). */
 const char* busca_build_info(void);
-/* Options of one context.  Defaults are read from the environment ONCE, at busca_ctx_create (BUSCA_DT_NTRK, BUSCA_DT_TILED, BUSCA_DT_SPLIT, BUSCA_CROP_BAND);
+/* Options of one context.  Defaults are read from the environment ONCE, at busca_ctx_create (BUSCA_DT_NTRK, BUSCA_DT_TILED, BUSCA_DT_SPLIT, BUSCA_CROP_BAND, ...);
  * no forward reads the environment.  Unknown name: BUSCA_EINVAL.
  *   "dt_ntrk"       0 auto / 1 / 2 tracks per workgroup of the f16 fused kernel (busca_amd.batcher pins it so that merged launches keep each step's flavour)
  *   "dt_tiled"      1 = force the layer-wise Decision-Transformer path (tests)
@@ -68,10 +68,10 @@ const char* busca_build_info(void);
  *                   non-finite BatchNorm statistics; nothing is clipped silently) - valid once the forwards' streams are synchronised; set 0 clears
  *   "crop_band"     1 = crops through the LDS-staged band kernel, 0 = one thread per output pixel (tests compare the two)
  *   get only: "last_dt_grid" / "last_dt_ntrk" / "last_dt_split" (workgroups, tracks per workgroup, token-split tracks of the last fused launch).
- * ReID schedule switches of a LOADED extractor that tests flip between two forwards (BUSCA_ENOWEIGHTS before weights are loaded): "reid_gram", "reid_halo",
- * "reid_fuse_c1", "reid_x3_fuse_c1", "reid_x3_gram_min", "reid_x3_merge_in_min", "reid_x3_row3", "reid_x3_ptail", "reid_x3_stem_halo", "reid_x3_stem_u8",
- * "reid_x3_stem_pool" (meanings: DESIGN.md section 5).  The remaining schedule thresholds are BUSCA_REID_* environment variables read by
- * busca_reid_load_weights (A/B runs). */
+ * "reid_*": ReID schedule switches of a LOADED extractor that tests flip between two forwards (set: BUSCA_ENOWEIGHTS before weights are loaded; flags read
+ * back as 0 / 1).  The list of record - option names, the BUSCA_REID_* environment variables busca_reid_load_weights reads (every knob has one; a reload starts
+ * again from defaults + environment), defaults and meanings - is the table REID_KNOBS in busca_amd/csrc/reid_state.hip.inc; the names above: BUSCA_OPTIONS in
+ * busca_amd/csrc/busca_hip.hip. */
 int busca_set_option(busca_ctx* ctx, const char* name, int32_t value);
 int busca_get_option(busca_ctx* ctx, const char* name, int32_t* value);
 

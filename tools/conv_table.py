@@ -14,14 +14,14 @@ out = []
 name, co, ci, k, s, p, bn = specs[0]
 out.append((ci, co, k, *osz(384, 128, k, s, p), "stem"))
 h, w, i = 96, 32, 1
-# launch order per bottleneck (capi_reid.hip.inc): conv1, conv2, [downsample], conv3 statistics pass, conv3 merge pass
+# launch order per bottleneck (reid_schedule.hip.inc): conv1, conv2, [downsample], conv3 statistics pass, conv3 merge pass
 for li, nb in enumerate((3, 4, 6, 3)):
     for b in range(nb):
         n1 = specs[i]; o1 = osz(h, w, n1[3], n1[4], n1[5]); out.append((n1[2], n1[1], n1[3], *o1, "conv1"))
         n2 = specs[i + 1]; o2 = osz(*o1, n2[3], n2[4], n2[5]); out.append((n2[2], n2[1], n2[3], *o2, "conv2"))
         n3 = specs[i + 2]; o3 = osz(*o2, n3[3], n3[4], n3[5])
         i += 3
-        gram = (not direct) and li <= 2 and n * o3[0] * o3[1] >= 65536      # capi_reid.hip.inc: reid_use_gram
+        gram = (not direct) and li <= 2 and n * o3[0] * o3[1] >= 65536      # reid_schedule.hip.inc: reid_use_gram
         if b == 0:
             nd = specs[i]; od = osz(h, w, nd[3], nd[4], nd[5]); i += 1
             if not gram: out.append((nd[2], nd[1], nd[3], *od, "down"))

@@ -86,7 +86,7 @@ int main(int argc, char** argv) {
         for (auto& v : hw) v = (_Float16)(frand() * wsc * 1.7f);
         for (int i = 0; i < c.Cin; ++i) { hss[2 * i] = 0.8f + 0.4f * frand(); hss[2 * i + 1] = 0.3f * frand(); hss2[2 * i] = 0.9f + 0.3f * frand(); hss2[2 * i + 1] = 0.2f * frand(); }
         if (c.stg == STG_MERGE) { hin2.resize(nin); for (auto& v : hin2) v = (_Float16)(frand() * 2.0f); }
-        // fragment order [Cout/16][half step h = 2 (tap*chunks + chunk) + kk][lane = 16b + a][8] (capi_reid.hip.inc)
+        // fragment order [Cout/16][half step h = 2 (tap*chunks + chunk) + kk][lane = 16b + a][8] (reid_weights.hip.inc)
         {
             const int taps = c.k * c.k, cch = c.Cin / 64, nhalf = 2 * taps * cch;
             for (int ct = 0; ct < c.Cout / 16; ++ct)
