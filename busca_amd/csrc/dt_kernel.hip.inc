@@ -1135,7 +1135,7 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
         if (p.argmax != nullptr && lane == 0) p.argmax[trk_] = bi;
     }
     if (PREC == 2 && clipped && p.xerr != nullptr) *p.xerr = 2;       // host-mapped: the next call reports it (busca_dt_forward)
-    DT_STAMP(4 + 12 * 4);
+    DT_STAMP(4 + 12 * DT_MAX_LAYERS);      // end of the kernel: behind the slots of every layer, whatever p.nlayers is
 }
 
 // Instantiations that crash hipcc's 'AMDGPU Rewrite AGPR-Copy-MFMA' pass (ROCm 7.2, -mllvm -amdgpu-mfma-vgpr-form) - which of the register-starved f16

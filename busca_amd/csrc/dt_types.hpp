@@ -39,7 +39,10 @@ struct DTParams {
     int nsingle; unsigned xepoch; unsigned long long* xch; unsigned* xflag; float* xlg; int* xerr;
     int can_pos, nspec, sep_can;   // token layout (busca_dt_cfg::layout): position of the CAN token in its (SEP, CAN) pair, special candidates (NON [, BAD]), SEP encoded with the candidate's box
 };
-#define DT_PROF_SLOTS 64
+// Phase-stamp slots per wave (BUSCA_DT_PROF): 0-3 the prologue, 4 + 12 l .. 15 + 12 l the phases of layer l, 4 + 12 DT_MAX_LAYERS the end of the kernel.
+// Sized from the layer limit (a power of two: the slot index is a shift) - with the former 64 a model of more than 4 layers stamped past the buffer.
+#define DT_PROF_SLOTS (16 * DT_MAX_LAYERS)
+static_assert(DT_PROF_SLOTS > 4 + 12 * DT_MAX_LAYERS, "the profile table must hold the last slot the fused kernel stamps");
 
 #define DT_X3_XS 64.0f     // split-fp16 flavour (Prec<2>, dt_kernel.hip.inc): activation / weight pre-scales (powers of two: exact)
 #define DT_X3_WS 256.0f

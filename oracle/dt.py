@@ -80,15 +80,18 @@ def mha(x, w_in, b_in, w_out, b_out, nhead):
     return F.linear(o, w_out, b_out), att
 
 
-def encoder_layer(x, sd, p, nhead, activation="relu"):
-    """custom_layers.py:30-41: post-norm, LayerNorm eps 1e-5; activation see DTConfig (ReLU in effect)."""
+def encoder_layer(x, sd, p, nhead, activation="relu", pre=None):
+    """custom_layers.py:30-41: post-norm, LayerNorm eps 1e-5; activation see DTConfig (ReLU in effect).
+    `pre`: a list that receives the feed-forward pre-activations linear1(x) of this layer (what the activation is applied to)."""
     act = F.relu if activation == "relu" else F.gelu
     d = x.shape[-1]
     a, att = mha(x, sd[p + "self_attn.in_proj_weight"], sd[p + "self_attn.in_proj_bias"],
                  sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"], nhead)
     x = F.layer_norm(x + a, (d,), sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-5)
-    h = F.linear(act(F.linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"])),
-                 sd[p + "linear2.weight"], sd[p + "linear2.bias"])
+    v = F.linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"])
+    if pre is not None:
+        pre.append(v)
+    h = F.linear(act(v), sd[p + "linear2.weight"], sd[p + "linear2.bias"])
     x = F.layer_norm(x + h, (d,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5)
     return x, att
 
@@ -97,7 +100,7 @@ def encoder_layer(x, sd, p, nhead, activation="relu"):
 def dt_forward(sd, cfg, mem_feat, can_feat, mem_boxes, can_boxes, luts=None, return_all=False):
     """Features [B,L,E],[B,P,E] + ltrb boxes [B,L,4],[B,P,4] -> logits [B,P+2] ([B,P+1] without BAD; pre-softmax, network.py:244).
 
-    return_all -> dict(logits, probs, argmax, hidden[B,T,d], att[list of B,h,T,T], bucket_ids[B,T,3])."""
+    return_all -> dict(logits, probs, argmax, hidden[B,T,d], att[list of B,h,T,T], bucket_ids[B,T,3], ffn_pre[list of B,T,ff])."""
     sd = _t(sd)
     mem_feat = torch.as_tensor(mem_feat, dtype=torch.float32)
     can_feat = torch.as_tensor(can_feat, dtype=torch.float32)
@@ -116,9 +119,9 @@ def dt_forward(sd, cfg, mem_feat, can_feat, mem_boxes, can_boxes, luts=None, ret
     if luts is None:
         luts = enc.build_luts(d)
     x = x + enc.encoding_rows(luts, ids[..., 0], ids[..., 1], ids[..., 2], d)  # encodings.py:87-88
-    atts = []
+    atts, pre = [], ([] if return_all else None)
     for i in range(cfg.nlayers):
-        x, att = encoder_layer(x, sd, "transformer_encoder.layers.%d." % i, cfg.nhead, cfg.activation)
+        x, att = encoder_layer(x, sd, "transformer_encoder.layers.%d." % i, cfg.nhead, cfg.activation, pre)
         atts.append(att)
     pos = can_positions(L, P, flavour)                          # network.py:142 CAN rows (incl. NON, BAD)
     out = x[:, pos]
@@ -127,4 +130,4 @@ def dt_forward(sd, cfg, mem_feat, can_feat, mem_boxes, can_boxes, luts=None, ret
     if not return_all:
         return logits
     probs = torch.softmax(logits, dim=-1)                        # network.py:96,403
-    return dict(logits=logits, probs=probs, argmax=probs.argmax(dim=-1), hidden=x, att=atts, bucket_ids=ids)
+    return dict(logits=logits, probs=probs, argmax=probs.argmax(dim=-1), hidden=x, att=atts, bucket_ids=ids, ffn_pre=pre)

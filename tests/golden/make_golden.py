@@ -7,6 +7,8 @@
     python tests/golden/make_golden.py reid_cfg4                              # round-3 set: 1 408-crop BatchNorm batches (~30 GB RAM, minutes)
     python tests/golden/make_golden.py dt512 assoc512 assoc_select reid_big   # round-2 sets (dt512/assoc512 need ~20 GB RAM;
                                                                               # not part of the default "all")
+    python tests/golden/make_golden.py dt_layers dt_gelu                      # layer counts other than 4; GELU with the reference's
+                                                                              # activation quirk repaired (not part of "all" either)
 
 The reference needs three import shims here: `cv2` and
 `positional_encodings` stubs from oracle/ref_shims/, and a no-network patch of
@@ -44,9 +46,9 @@ def import_reference():
     return ref_network, ref_tracking, ref_encodings
 
 
-def ref_args(d, ff, flavour="MEM-SEP-CAN-BAD"):
+def ref_args(d, ff, flavour="MEM-SEP-CAN-BAD", num_layer=4):
     return types.SimpleNamespace(
-        num_layer=4, nhead=4, dim_embedding=512, trans_dim=d, ff_size=ff, activation="gelu", dropout_p=0.1,
+        num_layer=num_layer, nhead=4, dim_embedding=512, trans_dim=d, ff_size=ff, activation="gelu", dropout_p=0.1,
         input_flavour=flavour, output_flavour="CAN", encode_separator_as_reference=True,
         encode_special_tokens=False, reid_weights_file="no", device=torch.device("cpu"))
 
@@ -234,6 +236,67 @@ def make_dt_geometry(ref):
         print("geometry case", name, r["logits"].shape, r["att"].shape)
         del model
     np.savez_compressed(os.path.join(OUT, "geometry_dt.npz"), **out)
+
+
+DT_LAYER_CASES = [
+    # name, d, nlayers, B, L, P, seed : layer counts other than the shipped 4 (ff = 2 d, nhead = 4; the reference as it is, hence ReLU)
+    ("d64_n1", 64, 1, 3, 11, 5, 51),
+    ("d64_n8", 64, 8, 3, 11, 5, 52),
+    ("d256_n1", 256, 1, 3, 11, 5, 53),
+    ("d256_n3", 256, 3, 3, 9, 16, 54),
+    ("d256_n8", 256, 8, 3, 11, 5, 55),
+]
+
+DT_GELU_CASES = [
+    # name, d, nlayers, B, L, P, seed : the configured GELU, with the deepcopy quirk of the cloned layers repaired at run time
+    ("d64_n4", 64, 4, 4, 11, 5, 61),
+    ("d64_n3", 64, 3, 3, 9, 4, 62),
+    ("d256_n4", 256, 4, 5, 11, 5, 63),
+    ("d256_n3", 256, 3, 3, 9, 16, 64),
+]
+
+
+def repair_activation_quirk(model):
+    """custom_layers.py:24-27,44-45: deepcopy puts F.relu into every clone's instance dict, which shadows the registered nn.GELU.
+    Removing that entry makes the clone fall back to the module it was configured with."""
+    for layer in model.transformer_encoder.layers:
+        del layer.__dict__["activation"]
+    for layer in model.transformer_encoder.layers:
+        assert type(layer.activation).__name__ == "GELU", type(layer.activation)
+
+
+def _run_config_cases(ref_network, cases, gelu, fname):
+    """One reference model per case (args.num_layer builds the encoder, network.py:84-86), float64 sentinel mode.
+    name/meta = d, ff, nhead, nlayers, activation (0 ReLU, 1 GELU), B, L, P, seed, float64 sentinel mode."""
+    out = {}
+    for name, d, nl, B, L, P, seed in cases:
+        model = ref_network.BUSCA(ref_args(d, 2 * d, num_layer=nl)).eval()
+        assert len(model.transformer_encoder.layers) == nl
+        if gelu:
+            repair_activation_quirk(model)
+        else:
+            assert all(getattr(layer.activation, "__name__", "") == "relu" for layer in model.transformer_encoder.layers)
+        load_dt_weights(model, synth.dt_state_dict(seed, d=d, ff=2 * d, nlayers=nl))
+        inp = synth.dt_inputs(seed, B, L, P, sentinel_every=4)
+        set_fake_dtype(model, True)
+        r = run_ref_dt(model, inp)
+        assert r["att"].shape[0] == nl
+        for k, v in r.items():
+            out["%s/%s" % (name, k)] = v
+        out[name + "/meta"] = np.array([d, 2 * d, 4, nl, int(gelu), B, L, P, seed, 1])
+        print(fname, "case", name, r["logits"].shape, r["att"].shape, flush=True)
+        del model
+    np.savez_compressed(os.path.join(OUT, fname), **out)
+
+
+def make_dt_layers(ref):
+    """args.num_layer in {1, 3, 8}: the one-layer model (first layer = last), an odd count and the most the kernels are built for."""
+    _run_config_cases(ref[0], DT_LAYER_CASES, False, "layers_dt.npz")
+
+
+def make_dt_gelu(ref):
+    """The reference with its activation quirk repaired (every clone runs its registered nn.GELU): pins the oracle's activation="gelu"."""
+    _run_config_cases(ref[0], DT_GELU_CASES, True, "gelu_dt.npz")
 
 
 class FakeTrack:
@@ -643,6 +706,10 @@ def main():
         make_dt_geometry(ref)
     if "dt_flavours" in which:
         make_dt_flavours(ref)
+    if "dt_layers" in which:
+        make_dt_layers(ref)
+    if "dt_gelu" in which:
+        make_dt_gelu(ref)
     if "dt512" in which:
         make_dt512(ref)
     if "assoc512" in which:

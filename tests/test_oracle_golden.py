@@ -103,6 +103,53 @@ def test_dt_other_head_counts_and_ff_widths_match_reference():
         np.testing.assert_allclose(att, g[name + "/att"], rtol=0, atol=2e-6, err_msg=name)
 
 
+def _config_cases(fname):
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", fname))
+    return g, sorted({k.split("/")[0] for k in g.files if "/" in k})
+
+
+def _check_config_file(fname, want_cases, want_act):
+    g, names = _config_cases(fname)
+    assert len(names) == want_cases
+    for name in names:
+        d, ff, nhead, nl, act, B, L, P, seed, f64 = (int(v) for v in g[name + "/meta"])
+        assert act == want_act and f64 == 1, name
+        sd = synth.dt_state_dict(seed, d=d, ff=ff, nlayers=nl)
+        inp = synth.dt_inputs(seed, B, L, P, sentinel_every=4)
+        cfg = odt.DTConfig(d=d, ff=ff, nhead=nhead, nlayers=nl, activation="gelu" if act else "relu")
+        o = odt.dt_forward(sd, cfg, **inp, return_all=True)
+        np.testing.assert_allclose(o["logits"].numpy(), g[name + "/logits"], rtol=0, atol=2e-5, err_msg=name)
+        np.testing.assert_allclose(o["probs"].numpy(), g[name + "/probs"], rtol=0, atol=2e-6, err_msg=name)
+        pos = odt.can_positions(L, P)
+        np.testing.assert_allclose(o["hidden"][:, pos].numpy(), g[name + "/can_hidden"], rtol=0, atol=5e-5, err_msg=name)
+        np.testing.assert_allclose(o["hidden"][:, :L].mean(1).numpy(), g[name + "/mem_hidden_mean"], rtol=0, atol=5e-5, err_msg=name)
+        att = np.stack([a.numpy() for a in o["att"]])
+        assert att.shape == g[name + "/att"].shape and att.shape[0] == nl, name
+        np.testing.assert_allclose(att, g[name + "/att"], rtol=0, atol=2e-6, err_msg=name)
+        srt = np.sort(g[name + "/probs"], axis=-1)
+        clear = (srt[:, -1] - srt[:, -2]) > 1e-5
+        assert (o["argmax"].numpy()[clear] == g[name + "/argmax"][clear]).all(), name
+    return g, names
+
+
+def test_dt_other_layer_counts_match_reference():
+    """args.num_layer in {1, 3, 8} (network.py:84-86; one layer, an odd count, the most the kernels take): the oracle against outputs
+    of the reference itself (tests/golden/make_golden.py dt_layers), attention maps of every layer included."""
+    g, names = _check_config_file("layers_dt.npz", 5, 0)
+    assert sorted({int(g[n + "/meta"][3]) for n in names}) == [1, 3, 8]
+
+
+def test_dt_gelu_matches_reference_with_the_quirk_repaired():
+    """The reference whose cloned layers run their registered nn.GELU (tests/golden/make_golden.py dt_gelu removes the F.relu that
+    deepcopy left in every clone's instance dict): pins DTConfig(activation="gelu").  The same weights with ReLU are far away."""
+    g, names = _check_config_file("gelu_dt.npz", 4, 1)
+    for name in names:
+        d, ff, nhead, nl, act, B, L, P, seed, f64 = (int(v) for v in g[name + "/meta"])
+        relu = odt.dt_forward(synth.dt_state_dict(seed, d=d, ff=ff, nlayers=nl), odt.DTConfig(d=d, ff=ff, nlayers=nl),
+                              **synth.dt_inputs(seed, B, L, P, sentinel_every=4)).numpy()
+        assert np.abs(relu - g[name + "/logits"]).max() > 0.12, name      # twice the f16 logit bar of the GPU suite: no flavour can pass with ReLU
+
+
 def test_reference_rejects_cls_flavours_and_mismatched_special_tokens():
     """What the reference itself does with the options this library refuses (recorded by tests/golden/make_golden.py dt_flavours)."""
     g, _ = _flavour_cases()
