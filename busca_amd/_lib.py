@@ -41,6 +41,10 @@ SIGNATURES = {
     "busca_coverage": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "busca_ecc_align": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_double, _vp, C.POINTER(C.c_double), C.POINTER(_i32), _vp]),
     "busca_kalman_multi_predict": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    "busca_kalman_update": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "busca_kalman_initiate": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "busca_kalman_boxes": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "busca_kalman_gating": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "busca_duplicate_masks": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "busca_crop_gather": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "busca_crop_gather_ex": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),

@@ -133,6 +133,52 @@ extern "C" int busca_kalman_multi_predict(busca_ctx* c, double* mean, double* co
     return BUSCA_OK;
 }
 
+extern "C" int busca_kalman_update(busca_ctx* c, double* mean, double* cov, const double* meas, int32_t n, int32_t* status, void* stream) {
+    if (!c) return BUSCA_EINVAL;
+    if (n < 0 || (n > 0 && (!mean || !cov || !meas))) return fail(c, BUSCA_EINVAL, "busca_kalman_update: bad argument");
+    if (n == 0) return BUSCA_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(kalman_update_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, mean, cov, meas, n, (int*)status);
+    HIP_TRY(c, hipGetLastError());
+    return BUSCA_OK;
+}
+
+extern "C" int busca_kalman_initiate(busca_ctx* c, const double* meas, int32_t n, double* mean, double* cov, void* stream) {
+    if (!c) return BUSCA_EINVAL;
+    if (n < 0 || (n > 0 && (!meas || !mean || !cov))) return fail(c, BUSCA_EINVAL, "busca_kalman_initiate: bad argument");
+    if (n == 0) return BUSCA_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(kalman_initiate_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, meas, n, mean, cov);
+    HIP_TRY(c, hipGetLastError());
+    return BUSCA_OK;
+}
+
+extern "C" int busca_kalman_boxes(busca_ctx* c, const double* mean, int32_t n, int32_t tlbr, double* out, void* stream) {
+    if (!c) return BUSCA_EINVAL;
+    if (n < 0 || (tlbr != 0 && tlbr != 1) || (n > 0 && (!mean || !out))) return fail(c, BUSCA_EINVAL, "busca_kalman_boxes: bad argument");
+    if (n == 0) return BUSCA_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(kalman_boxes_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, n, tlbr, out);
+    HIP_TRY(c, hipGetLastError());
+    return BUSCA_OK;
+}
+
+extern "C" int busca_kalman_gating(busca_ctx* c, const double* mean, const double* cov, int32_t n, const double* meas, int32_t m,
+                                   int32_t only_position, int32_t metric, double* out, int32_t* status, void* stream) {
+    if (!c) return BUSCA_EINVAL;
+    if (n < 0 || m < 0 || (only_position != 0 && only_position != 1) || (metric != 0 && metric != 1))
+        return fail(c, BUSCA_EINVAL, "busca_kalman_gating: bad argument");
+    if (n == 0 || m == 0) return BUSCA_OK;
+    if (!mean || !cov || !meas || !out) return fail(c, BUSCA_EINVAL, "busca_kalman_gating: null pointer");
+    const int tiles = (m + KALMAN_GATE_TILE - 1) / KALMAN_GATE_TILE;
+    if (tiles > 65535) return fail(c, BUSCA_EINVAL, "busca_kalman_gating: more than %d measurements", 65535 * KALMAN_GATE_TILE);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(kalman_gating_kernel, dim3(n, tiles), dim3(64), 0, (hipStream_t)stream, mean, cov, n, meas, m, only_position, metric, out,
+                       (int*)status);
+    HIP_TRY(c, hipGetLastError());
+    return BUSCA_OK;
+}
+
 extern "C" int busca_duplicate_masks(busca_ctx* c, const double* cost, int32_t nA, int32_t nB, const int32_t* ageA, const int32_t* ageB,
                                      double thresh, uint8_t* keepA, uint8_t* keepB, void* stream) {
     if (!c) return BUSCA_EINVAL;

@@ -76,6 +76,193 @@ def multi_predict(stracks, ctx=None):
         st.covariance = cov[i]
 
 
+CHI2INV95 = {2: 5.9915, 4: 9.4877}      # kalman_filter.py:10-19, the gates of only_position=True / False
+
+
+def tlwh_to_xyah(tlwh):
+    """STrack.tlwh_to_xyah (byte_tracker.py:165-172) of [n,4] boxes: (centre x, centre y, width / height, height)."""
+    ret = np.array(tlwh, dtype=np.float64).reshape(-1, 4)
+    ret[:, :2] += ret[:, 2:] / 2
+    ret[:, 2] /= ret[:, 3]
+    return ret
+
+
+def _measurements(detections):
+    """[m,4] float64 (x, y, a, h): an ndarray is taken as measurements already (what KalmanFilter.gating_distance takes),
+    detection objects give tlwh_to_xyah(det.tlwh) as `det.to_xyah()` does."""
+    if isinstance(detections, np.ndarray):
+        return np.ascontiguousarray(detections, dtype=np.float64).reshape(-1, 4)
+    return tlwh_to_xyah([d.tlwh for d in detections])
+
+
+def _upload_states(stracks, dev):
+    mean = torch.from_numpy(np.asarray([st.mean for st in stracks], dtype=np.float64).reshape(-1, 8)).to(dev)
+    cov = torch.from_numpy(np.asarray([st.covariance for st in stracks], dtype=np.float64).reshape(-1, 8, 8)).to(dev)
+    return mean, cov
+
+
+def _raise_flagged(status, what):
+    bad = np.nonzero(status)[0]
+    if len(bad):
+        raise np.linalg.LinAlgError("%s: the projected covariance of track %d is not positive definite (%d of %d tracks)"
+                                    % (what, int(bad[0]), len(bad), len(status)))
+
+
+def multi_update(stracks, detections, ctx=None):
+    """The Kalman step of STrack.update / re_activate (byte_tracker.py:78,109) for every matched pair at once:
+    `stracks[i].mean / .covariance` become KalmanFilter.update(mean, covariance, tlwh_to_xyah(detections[i].tlwh))
+    (kalman_filter.py:193-225).  Ids, memories and states stay with the tracker.  Where the reference raises LinAlgError (a
+    projected covariance that is not positive definite) this raises it too, naming the first such track - after every other
+    track of the call has been updated; the flagged ones keep their state."""
+    if len(stracks) != len(detections):
+        raise ValueError("multi_update pairs track i with detection i: got %d tracks and %d detections" % (len(stracks), len(detections)))
+    n = len(stracks)
+    if n == 0:
+        return
+    ctx = ctx or geometry.default_context()
+    dev = torch.device("cuda", ctx.device)
+    mean, cov = _upload_states(stracks, dev)
+    meas = torch.from_numpy(_measurements(detections)).to(dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.busca_kalman_update(ctx.h, mean.data_ptr(), cov.data_ptr(), meas.data_ptr(), n, status.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream))
+    both = torch.cat([mean, cov.view(n, 64), status.to(torch.float64).view(n, 1)], 1).cpu().numpy()     # one device->host copy for all three
+    mean, cov = np.ascontiguousarray(both[:, :8]), np.ascontiguousarray(both[:, 8:72]).reshape(-1, 8, 8)
+    for i, st in enumerate(stracks):
+        st.mean = mean[i]
+        st.covariance = cov[i]
+    _raise_flagged(both[:, 72], "multi_update")
+
+
+def multi_initiate(detections, ctx=None):
+    """KalmanFilter.initiate (kalman_filter.py:54-85) of every new detection, as STrack.activate calls it (byte_tracker.py:67):
+    -> (mean [n,8], covariance [n,8,8]) float64."""
+    meas = _measurements(detections)
+    n = meas.shape[0]
+    if n == 0:
+        return np.zeros((0, 8)), np.zeros((0, 8, 8))
+    ctx = ctx or geometry.default_context()
+    dev = torch.device("cuda", ctx.device)
+    z = torch.from_numpy(meas).to(dev)
+    both = torch.empty(n * 72, dtype=torch.float64, device=dev)
+    ctx.check(ctx.lib.busca_kalman_initiate(ctx.h, z.data_ptr(), n, both.data_ptr(), both.data_ptr() + 64 * n,
+                                            torch.cuda.current_stream(dev).cuda_stream))
+    host = both.cpu().numpy()
+    return host[:8 * n].reshape(n, 8).copy(), host[8 * n:].reshape(n, 8, 8).copy()
+
+
+_METRICS = {"maha": 0, "gaussian": 1}
+
+
+def _gating_dev(ctx, mean, cov, meas, only_position, metric):
+    """Device [n,m] gating distances and the [n] int32 status words of device states and measurements."""
+    n, m = mean.shape[0], meas.shape[0]
+    out = torch.empty(n, m, dtype=torch.float64, device=mean.device)
+    status = torch.zeros(n, dtype=torch.int32, device=mean.device)
+    ctx.check(ctx.lib.busca_kalman_gating(ctx.h, mean.data_ptr(), cov.data_ptr(), n, meas.data_ptr(), m, int(bool(only_position)), metric,
+                                          out.data_ptr(), status.data_ptr(), torch.cuda.current_stream(mean.device).cuda_stream))
+    return out, status
+
+
+def _download_with_status(mat, status, what):
+    """One device->host copy of a [n,m] matrix and its tracks' status words."""
+    n, m = mat.shape
+    host = torch.cat([mat.reshape(-1), status.to(torch.float64)]).cpu().numpy()
+    _raise_flagged(host[n * m:], what)
+    return host[:n * m].reshape(n, m).copy()
+
+
+def gating_distance(stracks, detections, only_position=False, metric="maha", ctx=None):
+    """KalmanFilter.gating_distance (kalman_filter.py:227-269) of every track against every detection: [n,m] float64, the
+    squared Mahalanobis ('maha') or squared Euclidean ('gaussian') distance between the track's projected state and
+    the detection's (x, y, a, h) - (x, y) only with `only_position`.  `detections`: objects with `.tlwh`, or an [m,4] array
+    of measurements.  Raises LinAlgError where np.linalg.cholesky does in the reference."""
+    if metric not in _METRICS:
+        raise ValueError("invalid distance metric")
+    meas = _measurements(detections)
+    n, m = len(stracks), meas.shape[0]
+    if n == 0 or m == 0:
+        return np.zeros((n, m), dtype=np.float64)
+    ctx = ctx or geometry.default_context()
+    dev = torch.device("cuda", ctx.device)
+    mean, cov = _upload_states(stracks, dev)
+    out, status = _gating_dev(ctx, mean, cov, torch.from_numpy(meas).to(dev), only_position, _METRICS[metric])
+    return _download_with_status(out, status, "gating_distance")
+
+
+def _gate_dev(cost, gate, only_position, lambda_):
+    """matching.py:141 / :154-155 on device tensors: inf above the chi-square gate, then (fuse_motion) the blend."""
+    cost = torch.where(gate > CHI2INV95[2 if only_position else 4], float("inf"), cost)
+    if lambda_ is not None:
+        cost = lambda_ * cost + (1 - lambda_) * gate
+    return cost
+
+
+def _gated(cost, stracks, detections, only_position, lambda_, ctx, what):
+    n, m = len(stracks), len(detections)
+    if n == 0 or m == 0:                                       # `if cost_matrix.size == 0: return cost_matrix`
+        return cost.cpu().numpy() if torch.is_tensor(cost) else cost
+    ctx = ctx or geometry.default_context()
+    dev = torch.device("cuda", ctx.device)
+    if not torch.is_tensor(cost):
+        cost = torch.from_numpy(np.ascontiguousarray(cost, dtype=np.float64))
+    cost = cost.to(device=dev, dtype=torch.float64).reshape(n, m)
+    mean, cov = _upload_states(stracks, dev)
+    gate, status = _gating_dev(ctx, mean, cov, torch.from_numpy(_measurements(detections)).to(dev), only_position, 0)
+    return _download_with_status(_gate_dev(cost, gate, only_position, lambda_), status, what)
+
+
+def gate_cost_matrix(cost, stracks, detections, only_position=False, ctx=None):
+    """matching.gate_cost_matrix (adapters/ByteTrack/yolox/tracker/matching.py:132-142): entries whose squared Mahalanobis
+    distance exceeds chi2inv95[4] = 9.4877 (chi2inv95[2] = 5.9915 with `only_position`) become inf.  `cost`: [n,m] host array
+    or a device tensor (geometry.pairwise) - the gate is applied on the device either way.  Returns a new host array."""
+    return _gated(cost, stracks, detections, only_position, None, ctx, "gate_cost_matrix")
+
+
+def fuse_motion(cost, stracks, detections, only_position=False, lambda_=0.98, ctx=None):
+    """matching.fuse_motion (matching.py:145-156): the gate of gate_cost_matrix, then lambda_ * cost + (1 - lambda_) * distance.
+    Gating distances, gate and blend all stay on the device; one device->host copy of the result."""
+    return _gated(cost, stracks, detections, only_position, float(lambda_), ctx, "fuse_motion")
+
+
+def predicted_cost(stracks, detections, det_scores=None, fuse_motion=False, only_position=False, lambda_=0.98, ctx=None):
+    """One association round's cost matrix without leaving the device: STrack.multi_predict (busca_kalman_multi_predict) ->
+    the predicted boxes (busca_kalman_boxes, tlbr) -> iou_distance, with fuse_score when `det_scores` is given (busca_pairwise
+    IOU_COST) -> with `fuse_motion`, matching.fuse_motion on the predicted states (busca_kalman_gating + gate + blend).
+    The tracks get their predicted `mean` / `covariance` as multi_predict gives them; the [n,m] cost matrix comes back in the
+    same single device->host copy.  `detections`: objects with `.tlbr` and `.tlwh`."""
+    n, m = len(stracks), len(detections)
+    if n == 0:
+        return np.zeros((0, m), dtype=np.float64)
+    ctx = ctx or geometry.default_context()
+    dev = torch.device("cuda", ctx.device)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    mean, cov = _upload_states(stracks, dev)
+    nt = torch.from_numpy(np.asarray([st.state != TRACKED for st in stracks], dtype=np.uint8)).to(dev)
+    ctx.check(ctx.lib.busca_kalman_multi_predict(ctx.h, mean.data_ptr(), cov.data_ptr(), nt.data_ptr(), n, stream))
+    parts = [mean.view(-1), cov.view(-1)]
+    if m > 0:
+        boxes = torch.empty(n, 4, dtype=torch.float64, device=dev)
+        ctx.check(ctx.lib.busca_kalman_boxes(ctx.h, mean.data_ptr(), n, 1, boxes.data_ptr(), stream))
+        cost = geometry.pairwise(ctx, boxes, _tlbrs(detections), _lib.PAIR_IOU_COST, scores_b=det_scores)
+        if fuse_motion:
+            gate, status = _gating_dev(ctx, mean, cov, torch.from_numpy(_measurements(detections)).to(dev), only_position, 0)
+            cost = _gate_dev(cost, gate, only_position, float(lambda_))
+            parts += [cost.view(-1), status.to(torch.float64)]
+        else:
+            parts.append(cost.view(-1))
+    host = torch.cat(parts).cpu().numpy()                        # one device->host copy: states, cost matrix, status words
+    pm, pc = host[:8 * n].reshape(n, 8).copy(), host[8 * n:72 * n].reshape(n, 8, 8).copy()
+    for i, st in enumerate(stracks):
+        st.mean = pm[i]
+        st.covariance = pc[i]
+    if m == 0:
+        return np.zeros((n, 0), dtype=np.float64)
+    if fuse_motion:
+        _raise_flagged(host[72 * n + n * m:], "predicted_cost")
+    return host[72 * n:72 * n + n * m].reshape(n, m).copy()
+
+
 def remove_duplicate_stracks(stracksa, stracksb, ctx=None, thresh=0.15):
     """remove_duplicate_stracks (byte_tracker.py:685-698): of two tracks whose IoU cost is below 0.15 the one alive for
     fewer frames goes (ties: the one of the first list).  IoU cost and the marking both run on the GPU."""

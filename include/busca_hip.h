@@ -192,6 +192,25 @@ int busca_ecc_align(busca_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int
  * adapters/CenterTrack/src/lib/utils/mot_online/kalman_filter.py:154-190 - the copy byte_tracker.py:15 falls back to).
  * Bit-exact against the numpy evaluation. */
 int busca_kalman_multi_predict(busca_ctx* ctx, double* mean, double* cov, const uint8_t* not_tracked, int32_t n, void* stream);
+/* KalmanFilter.project + update (kalman_filter.py:125-152,193-225; STrack.update / re_activate, byte_tracker.py:78,109): the
+ * measurement update of n tracks in place.  meas dev f64 [n,4] (x,y,a,h) = tlwh_to_xyah of the matched detection (:165-172).
+ * status dev i32 [n] or NULL: 0 = updated; 1 = the innovation covariance has a pivot that is not positive and finite (the
+ * reference raises LinAlgError in scipy.linalg.cho_factor) and the track's mean and covariance are left as they were.
+ * Same formulas as the reference's LAPACK route in another float64 order (sums left to right): not bit-exact. */
+int busca_kalman_update(busca_ctx* ctx, double* mean, double* cov, const double* meas, int32_t n, int32_t* status, void* stream);
+/* KalmanFilter.initiate (kalman_filter.py:54-85; STrack.activate, byte_tracker.py:67): mean [n,8] = (meas, 0), cov [n,8,8] =
+ * diag(square(2h/20, 2h/20, 1e-2, 2h/20, 10h/160, 10h/160, 1e-5, 10h/160)), h = meas[3].  Bit-exact against the numpy evaluation. */
+int busca_kalman_initiate(busca_ctx* ctx, const double* meas, int32_t n, double* mean, double* cov, void* stream);
+/* STrack.tlwh (tlbr = 0) / STrack.tlbr (tlbr = 1) of n states (byte_tracker.py:142-163): out dev f64 [n,4], ready to be an operand
+ * of busca_pairwise.  Bit-exact against the numpy evaluation. */
+int busca_kalman_boxes(busca_ctx* ctx, const double* mean, int32_t n, int32_t tlbr, double* out, void* stream);
+/* KalmanFilter.gating_distance (kalman_filter.py:227-269; gate_cost_matrix / fuse_motion, matching.py:132-156) of every track
+ * against every measurement: out dev f64 [n,m]; meas dev f64 [m,4] (x,y,a,h).  metric 0 = squared Mahalanobis distance ('maha'),
+ * 1 = squared Euclidean distance ('gaussian'); only_position = 1 uses (x,y) and the leading 2x2 block of the projected covariance.
+ * status dev i32 [n] or NULL: 1 = the projected covariance is not positive definite (np.linalg.cholesky raises LinAlgError) and
+ * row t of out is NaN; always 0 for metric 1.  Not bit-exact (see busca_kalman_update). */
+int busca_kalman_gating(busca_ctx* ctx, const double* mean, const double* cov, int32_t n, const double* meas, int32_t m,
+                        int32_t only_position, int32_t metric, double* out, int32_t* status, void* stream);
 /* remove_duplicate_stracks (byte_tracker.py:685-698) on an IoU-cost matrix cost[nA,nB] (dev f64, busca_pairwise
  * IOU_COST): for every pair with cost < thresh (0.15) the track with the smaller age (frame_id - start_frame, dev i32)
  * is dropped; ties drop the A track.  keep_a [nA], keep_b [nB] dev u8: 1 = keep. */
