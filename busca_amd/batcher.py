@@ -52,25 +52,26 @@ class StepBatcher:
         return t
 
     def flush(self):
-        """Run every queued step: one busca_dt_forward per (L, P) group, then the per-step scatter."""
+        """Run every queued step: one busca_dt_forward per (L, P) group, settled as a whole (BUSCA._settle_steps), then the per-step scatter."""
         m = self.model
         pending, self._pending = self._pending, []
         groups = {}
         for t in pending:
-            groups.setdefault((t._job["L"], t._job["P"]), []).append(t)
+            groups.setdefault((t._job["step"].L, t._job["step"].P), []).append(t)
         launches = []
         for (L, P), ts in groups.items():
-            small = [t for t in ts if t._job["B"] <= 256]
+            small = [t for t in ts if t._job["step"].B <= 256]
             if small:
                 launches.append((small, 1))                       # one-track flavour, as each of these steps would run alone
-            launches.extend(([t], 0) for t in ts if t._job["B"] > 256)
+            launches.extend(([t], 0) for t in ts if t._job["step"].B > 256)
         for ts, ntrk in launches:
             feats = [m._assoc_features(t._job) for t in ts]
+            steps = [t._job["step"] for t in ts]
             dev = feats[0][0].device
             mem_feat = torch.cat([f[0] for f in feats], 0)
             can_feat = torch.cat([f[1] for f in feats], 0)
-            mem_ltrb = torch.cat([torch.from_numpy(t._job["mem_ltrb"]) for t in ts], 0).pin_memory().to(dev, non_blocking=True)
-            can_ltrb = torch.cat([torch.from_numpy(t._job["can_ltrb"]) for t in ts], 0).pin_memory().to(dev, non_blocking=True)
+            mem_ltrb = torch.cat([torch.from_numpy(s.mem_ltrb) for s in steps], 0).pin_memory().to(dev, non_blocking=True)
+            can_ltrb = torch.cat([torch.from_numpy(s.can_ltrb) for s in steps], 0).pin_memory().to(dev, non_blocking=True)
             prev = m._ctx.get_option("dt_ntrk")                   # a pin (BUSCA_DT_NTRK / an earlier set_option) outranks the batcher's choice and survives it
             m._ctx.set_option("dt_ntrk", prev if prev != 0 else ntrk)
             try:
@@ -79,12 +80,6 @@ class StepBatcher:
                 m._ctx.set_option("dt_ntrk", prev)
             self.launches += 1
             torch.cuda.current_stream(dev).synchronize()
-            out = m._dt.settle(out)             # a merged x3 launch that clipped an operand is run again in exact float32 before it is handed out
-            reid_overflow = m._reid.take_status()       # (one status word per context: every step of this flush is suspect when an x3 ReID pass overflowed)
-            lo = 0
-            for t in ts:
-                hi = lo + t._job["B"]
-                part = {k: v[lo:hi] for k, v in out.items()}
-                t._value, t._done = m._assoc_finish(t._job, part, reid_overflow), True
-                lo = hi
+            for t, part in zip(ts, m._settle_steps(out, steps)):       # an x3 launch that left its range is run again before it is handed out
+                t._value, t._done = m._assoc_scatter(t._job, part), True
                 self.steps += 1

@@ -8,7 +8,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib, weights
+from . import _lib, geometry, weights
 
 _PREC = {"f32": _lib.PREC_F32, "f16": _lib.PREC_F16, "x3": _lib.PREC_F16X3}      # x3: float32-equivalent split-fp16 GEMMs (dt_kernel.hip.inc, Prec<2>)
 _ACT = {"relu": _lib.ACT_RELU, "gelu": _lib.ACT_GELU}
@@ -22,6 +22,12 @@ def layout_bits(input_flavour, encode_separator_as_reference=True):
         raise NotImplementedError('Input flavour "{}" not implemented'.format(input_flavour))
     return ((_lib.LAYOUT_CAN_FIRST if "MEM-CAN-SEP" in input_flavour else 0) | (0 if "BAD" in input_flavour else _lib.LAYOUT_NO_BAD)
             | (0 if encode_separator_as_reference else _lib.LAYOUT_SEP_AS_CAN))
+
+
+class DTOutput(dict):
+    """What `DecisionTransformerHIP.forward` returns: the dict of output tensors, plus what is needed to compute them again."""
+    rerun = None        # x3: (mem_feat, can_feat, mem_ltrb, can_ltrb, want_hidden, want_att, stream) as staged, for settle() - alive exactly as long as the output
+    step = None         # busca_amd.network attaches its record of the step here (BUSCA.settle)
 
 
 class DecisionTransformerHIP:
@@ -46,7 +52,6 @@ class DecisionTransformerHIP:
                                   "d/nhead in 16/32/64/128, ff a multiple of d up to 8 d, E = 512)" % (d, ff, self.nhead, nl, E))
         assert self._blob.size == want, (self._blob.size, want)
         self._luts = weights.encoding_luts(d)
-        self._rerun = {}            # x3: id(logits) -> (weakref, inputs) of forwards not settled yet (see settle)
         self.exact_reruns = 0       # steps settle() re-ran in exact float32 because the x3 forward reported a clipped operand
         self._upload()
 
@@ -64,26 +69,26 @@ class DecisionTransformerHIP:
             self._upload()
 
     @staticmethod
-    def _f32(t, dev):
+    def _f32(t, dev, stream=None):
         if not torch.is_tensor(t):
             t = torch.as_tensor(np.asarray(t))
-        if t.device.type == "cpu":      # host boxes / features: pinned staging + asynchronous copy (a pageable `.to` parks the host behind everything queued on the stream)
-            t = t.to(torch.float32).contiguous().pin_memory().to(dev, non_blocking=True)
+        if t.device.type == "cpu":      # host boxes / features: staged on the stream the kernels run on
+            t = geometry.h2d_async(t.to(torch.float32), dev, stream)
         return t.to(device=dev, dtype=torch.float32).contiguous()
 
     def forward(self, mem_feat, can_feat, mem_ltrb, can_ltrb, want_hidden=False, want_att=False, stream=None):
-        """-> dict(logits[B,P+2], probs[B,P+2], argmax[B] int32, hidden?[B,T,d], att?[nl,B,nhead,T,T]); P+1 columns without the BAD token."""
+        """-> DTOutput(logits[B,P+2], probs[B,P+2], argmax[B] int32, hidden?[B,T,d], att?[nl,B,nhead,T,T]); P+1 columns without the BAD token."""
         self._ensure_loaded()
         dev = torch.device("cuda", self.ctx.device)
-        mem_feat, can_feat = self._f32(mem_feat, dev), self._f32(can_feat, dev)
-        mem_ltrb, can_ltrb = self._f32(mem_ltrb, dev), self._f32(can_ltrb, dev)
+        mem_feat, can_feat = self._f32(mem_feat, dev, stream), self._f32(can_feat, dev, stream)
+        mem_ltrb, can_ltrb = self._f32(mem_ltrb, dev, stream), self._f32(can_ltrb, dev, stream)
         B, L, E = mem_feat.shape
         P = can_feat.shape[1]
         assert E == self.E and can_feat.shape == (B, P, E) and mem_ltrb.shape == (B, L, 4) and can_ltrb.shape == (B, P, 4)
         n = P + self.nspec
         T = L + 2 * n
-        out = dict(logits=torch.empty(B, n, device=dev), probs=torch.empty(B, n, device=dev),
-                   argmax=torch.empty(B, dtype=torch.int32, device=dev))
+        out = DTOutput(logits=torch.empty(B, n, device=dev), probs=torch.empty(B, n, device=dev),
+                       argmax=torch.empty(B, dtype=torch.int32, device=dev))
         if want_hidden:
             out["hidden"] = torch.empty(B, T, self.d, device=dev)
         if want_att:
@@ -93,10 +98,8 @@ class DecisionTransformerHIP:
             self.ctx.h, mem_feat.data_ptr(), can_feat.data_ptr(), mem_ltrb.data_ptr(), can_ltrb.data_ptr(), B, L, P,
             out["logits"].data_ptr(), out["probs"].data_ptr(), out["argmax"].data_ptr(),
             _lib.ptr(out.get("hidden")), _lib.ptr(out.get("att")), s))
-        if self.precision == "x3":     # what settle() needs to run the step once more (keeps the inputs alive as long as the outputs)
-            self._rerun[id(out["logits"])] = (weakref.ref(out["logits"]), (mem_feat, can_feat, mem_ltrb, can_ltrb, want_hidden, want_att, stream))
-            if len(self._rerun) > 64:
-                self._rerun = {k: v for k, v in self._rerun.items() if v[0]() is not None}
+        if self.precision == "x3":     # what settle() needs to run the step once more
+            out.rerun = (mem_feat, can_feat, mem_ltrb, can_ltrb, want_hidden, want_att, stream)
         return out
 
     def settle(self, out):
@@ -110,15 +113,11 @@ class DecisionTransformerHIP:
         The status is cleared either way, so the C-side backstop of the next busca_dt_forward stays silent."""
         st = self.ctx.get_option("dt_status")
         if st == 0:
-            self._rerun.pop(id(out["logits"]), None)
             return out
         self.ctx.set_option("dt_status", 0)
         if st != 2:
             raise _lib.BuscaError("a token-split Decision-Transformer launch gave up waiting for a partner workgroup: the results of this forward are invalid")
-        ent = self._rerun.pop(id(out["logits"]), None)
-        if ent is None or ent[0]() is not out["logits"]:
-            raise _lib.BuscaError("an x3 Decision-Transformer forward clipped an operand (|x| > 1023.5) and its inputs are gone: load the model with precision='f32'")
-        mem_feat, can_feat, mem_ltrb, can_ltrb, want_hidden, want_att, stream = ent[1]
+        mem_feat, can_feat, mem_ltrb, can_ltrb, want_hidden, want_att, stream = out.rerun
         self.exact_reruns += 1
         self.ctx.set_option("dt_exact_f32", 1)
         try:
@@ -126,7 +125,6 @@ class DecisionTransformerHIP:
             fixed = self.forward(mem_feat, can_feat, mem_ltrb, can_ltrb, want_hidden=want_hidden, want_att=want_att, stream=stream)
         finally:
             self.ctx.set_option("dt_exact_f32", 0)
-        self._rerun.pop(id(fixed["logits"]), None)
         if stream is None:
             torch.cuda.current_stream(torch.device("cuda", self.ctx.device)).synchronize()
         else:

@@ -7,13 +7,13 @@ step), token embed/assembly, bucket encoding, the 4 encoder layers, decoder, sof
 There is no CPU compute path: without the HIP library / a GPU every compute call raises.
 """
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
 
 from . import _lib, geometry, synth, tracking, weights
-from .dt import DecisionTransformerHIP
+from .dt import DecisionTransformerHIP, DTOutput
 from .reid import ReIDEncoderHIP
 
 _FLAVOURS = ("MEM-SEP-CAN-BAD", "MEM-SEP-CAN", "MEM-CAN-SEP-BAD", "MEM-CAN-SEP")   # network.py:103-165 without the CLS- ones
@@ -30,6 +30,12 @@ def _side_stream_of(dev):
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(dev)
     return _SIDE_STREAMS[key]
+
+
+# What ran for one step, attached to its DTOutput as `out.step` - all `BUSCA.settle` needs to run it again and to publish it.
+# reid: the two BatchNorm batches ((u8, zero_norm, weights) of the memory crops, the same of the candidate crops), None for a step on given features;
+# mem_inv / can_inv: the slot of the [B, L] / [B, P] grid each feature row of those batches stands for; mem_ltrb / can_ltrb: the boxes.
+_Step = namedtuple("_Step", "reid mem_inv can_inv B L P mem_ltrb can_ltrb")
 
 
 def memory_indices(n_hist, seq_len, use_broader_memory):
@@ -119,6 +125,11 @@ class BUSCA:
         self._dt = None
         self._reid = None
         self._dirty = True
+        self._reid_exact = None             # exact-f32 extractor of the same weights, built by the first x3 ReID pass that overflows (settle)
+        self.reid_exact_reruns = 0          # steps settle() ran again on it
+        self._side_stream = None
+        self._last = None                   # the DTOutput of the latest step
+        self.last_gather = self.last_unique = (0, 0)
         seed = int(getattr(args, "seed", 0))
         sd = OrderedDict(synth.dt_state_dict(seed, d=args.trans_dim, ff=args.ff_size, nlayers=args.num_layer, flavour=args.input_flavour))
         reid_sd = None
@@ -148,8 +159,15 @@ class BUSCA:
     def to(self, device):
         idx = self._index_of(device)
         if idx != self._device_index:
-            self._device_index, self._ctx, self._dt, self._reid, self._dirty = idx, None, None, None, True
+            self._device_index = idx
+            self._drop_device_state(device_changed=True)
         return self
+
+    def _drop_device_state(self, device_changed=False):
+        """The weights changed (or the device did): everything built from them on the device is rebuilt by the next `_sync()` / fallback."""
+        self._dirty, self._reid_exact = True, None
+        if device_changed:
+            self._ctx = self._dt = self._reid = self._side_stream = None
 
     def eval(self):
         return self
@@ -174,7 +192,7 @@ class BUSCA:
                 if arr.shape != self._sd[k].shape:
                     raise RuntimeError("size mismatch for {}: {} vs {}".format(k, arr.shape, self._sd[k].shape))
                 self._sd[k] = np.ascontiguousarray(arr)
-        self._dirty = True
+        self._drop_device_state()
 
     @staticmethod
     def _ignorable(key):
@@ -251,9 +269,7 @@ class BUSCA:
         dev = self._dev()
         n_can = max_lost * num_candidates if max_detections is None else min(max_lost * num_candidates, max_detections + max_lost + 1)
         self._reid.reserve(max_lost * seq_len)
-        if getattr(self, "_side_stream", None) is None:
-            self._side_stream = _side_stream_of(dev)
-        self._reid.reserve(max(1, n_can), stream=self._side_stream.cuda_stream)
+        self._reid.reserve(max(1, n_can), stream=self._side(dev).cuda_stream)
         self._dt.reserve(max_lost, seq_len, num_candidates)
 
     def _dev(self):
@@ -287,13 +303,7 @@ class BUSCA:
         """Enqueue one BatchNorm batch on the side stream (ordered after everything already on the current stream)."""
         dev = self._dev()
         cur = torch.cuda.current_stream(dev)
-        if getattr(self, "_side_stream", None) is None:
-            # ONE side stream per device and process, shared by every model: HIP deals streams to its few hardware queues
-            # round-robin, and a side stream that lands on the queue of the current stream serialises the two ReID passes of a
-            # step (4.4 -> 5.9 ms; seen on about one model instance in four when every instance made its own stream - a
-            # high-priority stream was worse, 7.8 ms).  The first stream a process creates sits next to the default queue.
-            self._side_stream = _side_stream_of(dev)
-        side = self._side_stream
+        side = self._side(dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             feat = self._reid.forward(u8, stream=side.cuda_stream, zero_norm=zero_norm, weights=weights)
@@ -301,6 +311,15 @@ class BUSCA:
         if zero_norm is not None:
             zero_norm.record_stream(side)
         return feat
+
+    def _side(self, dev):
+        if self._side_stream is None:
+            # ONE side stream per device and process, shared by every model: HIP deals streams to its few hardware queues
+            # round-robin, and a side stream that lands on the queue of the current stream serialises the two ReID passes of a
+            # step (4.4 -> 5.9 ms; seen on about one model instance in four when every instance made its own stream - a
+            # high-priority stream was worse, 7.8 ms).  The first stream a process creates sits next to the default queue.
+            self._side_stream = _side_stream_of(dev)
+        return self._side_stream
 
     def _reid_join(self, side_feat, cur_feat):
         """Make the current stream wait for the side-stream batch; returns (cur_feat, side_feat)."""
@@ -313,33 +332,82 @@ class BUSCA:
     def forward(self, embeddings_memory, candidate_embedding, memory_bboxes=None, candidates_bboxes=None,
                 return_att=False, return_logits=False, plot_results=False):
         """busca/network.py:176-244.  Images: u8 BGR [B,n,384,128,3] or normalised float RGB [B,n,3,384,128];
-        boxes ltrb [B,n,4].  Returns the pre-softmax logits [B,P+2] (a cuda tensor)."""
+        boxes ltrb [B,n,4].  Returns the pre-softmax logits [B,P+2] (a cuda tensor), asynchronously and unsettled: a caller whose checkpoint
+        may leave the x3 range synchronises and takes the result from `settle(model._last)`."""
         if plot_results:
             raise NotImplementedError("plot_results needs the reference's OpenCV visualisation")
         self._sync()
         B, L = int(embeddings_memory.shape[0]), int(embeddings_memory.shape[1])
         P = int(candidate_embedding.shape[1])
-        mem_feat, can_feat = self._reid_pair(self._to_u8_hwc_bgr(embeddings_memory), self._to_u8_hwc_bgr(candidate_embedding))
+        mem_u8, can_u8 = self._to_u8_hwc_bgr(embeddings_memory), self._to_u8_hwc_bgr(candidate_embedding)
+        mem_feat, can_feat = self._reid_pair(mem_u8, can_u8)
         mem_feat, can_feat = mem_feat.view(B, L, -1), can_feat.view(B, P, -1)     # two BN batches (network.py:192-193)
         out = self._dt.forward(mem_feat, can_feat, memory_bboxes, candidates_bboxes,
                                want_hidden=return_logits, want_att=return_att)
-        self._last = out
-        if return_att:
-            self.attentions = [out["att"][i] for i in range(out["att"].shape[0])]
-        if return_logits:
-            pos = self._dt.can_positions(L, P)
-            self.logits = out["hidden"][:, pos]
-            self.mem_logits = out["hidden"][:, :L].mean(dim=1)
+        out.step = _Step(((mem_u8, None, None), (can_u8, None, None)), np.arange(B * L), np.arange(B * P), B, L, P, memory_bboxes, candidates_bboxes)
+        self._publish(out)
         return out["logits"]
 
     __call__ = forward
 
     def forward_features(self, mem_feat, can_feat, memory_bboxes, candidates_bboxes, return_att=False, return_logits=False):
-        """Decision-Transformer step on precomputed 512-d ReID features (the 'DT-step' of bench.py)."""
+        """Decision-Transformer step on precomputed 512-d ReID features (the 'DT-step' of bench.py).  Asynchronous and unsettled, like `forward`."""
         self._sync()
         out = self._dt.forward(mem_feat, can_feat, memory_bboxes, candidates_bboxes, want_hidden=return_logits, want_att=return_att)
+        out.step = _Step(None, None, None, int(mem_feat.shape[0]), int(mem_feat.shape[1]), int(can_feat.shape[1]), memory_bboxes, candidates_bboxes)
         self._last = out
         return out
+
+    # ---- the fallbacks of the x3 flavours ------------------------------------------------------------------------------
+    def settle(self, out):
+        """Call once the stream of `out`'s step is SYNCHRONISED and before its results are used; returns the output to use.  The x3 flavours carry
+        |x| <= 1023.5; a step that left that range is computed again where it did, and only there:
+          an x3 ReID pass overflowed (`reid_status`)  -> both BatchNorm batches on the exact-f32 extractor and the Decision Transformer on those features -
+                                                         what `reid_precision="f32"` computes for the step, synchronised;
+          the x3 Decision Transformer clipped (`dt_status`) -> `DecisionTransformerHIP.settle`: the step again in exact float32, synchronised.
+        `_last` / `logits` / `mem_logits` / `attentions` then follow the result.  A healthy step comes back as it is, for two reads of host-mapped words."""
+        return self._settle_steps(out, [out.step])[0]
+
+    def _settle_steps(self, out, steps):
+        """`out`: ONE Decision-Transformer launch over the tracks of `steps`, in order (StepBatcher.flush; `settle` is the case of one step)
+        -> the settled output of every step.  Both status words belong to the context, not to a step: an overflowed ReID pass makes every
+        step of the launch suspect and each is computed again on its own; a clipped launch is run again once, as a whole."""
+        if self._reid.take_status() and steps[0].reid is not None:
+            self._ctx.set_option("dt_status", 0)            # (whatever the discarded forward on the invalid features left behind)
+            outs = [self._dt.settle(self._exact_reid_step(s, "hidden" in out, "att" in out)) for s in steps]
+        else:
+            out = self._dt.settle(out)
+            outs = [out]
+            if len(steps) > 1:                  # the tracks of each step, in the order they were concatenated
+                ends = np.cumsum([s.B for s in steps])
+                outs = [DTOutput((k, v[e - s.B:e]) for k, v in out.items()) for s, e in zip(steps, ends)]
+        for o, s in zip(outs, steps):
+            o.step = s
+            self._publish(o)
+        return outs
+
+    def _exact_reid_step(self, step, want_hidden, want_att):
+        """The two BatchNorm batches of `step` on the exact-f32 extractor (its own busca_ctx: a context holds ONE ReID weight set; created on first use)
+        and the Decision Transformer on those features, synchronised."""
+        if self._reid_exact is None:
+            self._reid_exact = ReIDEncoderHIP(_lib.Context(self._device_index), self._sd, prefix=_REID_PREFIX, precision="f32")
+        self.reid_exact_reruns += 1
+        (mu8, mzn, mw), (cu8, czn, cw) = step.reid
+        mem_feat = self._reid_exact.forward(mu8, zero_norm=mzn, weights=mw)
+        can_feat = self._reid_exact.forward(cu8, zero_norm=czn, weights=cw)
+        mem_feat, can_feat = self._slots(step, mem_feat, can_feat)
+        out = self._dt.forward(mem_feat, can_feat, step.mem_ltrb, step.can_ltrb, want_hidden=want_hidden, want_att=want_att)
+        torch.cuda.current_stream(self._dev()).synchronize()
+        return out
+
+    def _publish(self, out):
+        self._last = out
+        if "hidden" in out:                     # asked for through store_logits / return_logits
+            L = out.step.L
+            self.logits = out["hidden"][:, self._dt.can_positions(L, out.step.P)]
+            self.mem_logits = out["hidden"][:, :L].mean(dim=1)
+        if "att" in out:
+            self.attentions = [out["att"][i] for i in range(out["att"].shape[0])]
 
     # ---- batching of tracker objects (busca/network.py:282-429) ------------------------------------------
     def associate_embeddings(self, tracks_embeddings, dets_embeddings, dists_matrix, seq_len, num_candidates,
@@ -351,14 +419,17 @@ class BUSCA:
         if job is None:
             return None, None
         mem_feat, can_feat = self._assoc_features(job)
-        out = self._dt.forward(mem_feat, can_feat, job["mem_ltrb"], job["can_ltrb"], want_hidden=self.store_logits)
-        return self._assoc_finish(job, out)
+        step = job["step"]
+        out = self._dt.forward(mem_feat, can_feat, step.mem_ltrb, step.can_ltrb, want_hidden=self.store_logits)
+        out.step = step
+        torch.cuda.current_stream(self._dev()).synchronize()
+        return self._assoc_scatter(job, self.settle(out))     # an x3 step that left its range is run again: the tracker never gets a clipped step
 
     def _assoc_prepare(self, tracks_embeddings, dets_embeddings, dists_matrix, seq_len, num_candidates, use_broader_memory,
                        select_highest_candidate, highest_candidate_minimum_thresh=None, keep_highest_value=False,
                        extra_kalman_candidates=(), plot_results=False, normalize_ims=False):
         """Host bookkeeping of network.py:293-398 + the two ReID passes ENQUEUED (memory batch on the side stream, candidate
-        batch on the current one).  Returns the job (dict) that `_assoc_features` / `_assoc_finish` complete, or None for the
+        batch on the current one).  Returns the job (dict) that `_assoc_features` / `_assoc_scatter` complete, or None for the
         reference's early returns.  Split from the Decision-Transformer launch so that `StepBatcher` can run ONE launch for
         the steps of several trackers."""
         B, N, P, L = len(tracks_embeddings), len(dets_embeddings), int(num_candidates), int(seq_len)
@@ -439,61 +510,29 @@ class BUSCA:
         can_u8, can_zn, can_w, can_inv = self._gather_crops(can_ref, as_u8, zero_is_normalised)
         self.last_gather = (gathered[0] + self.last_gather[0], gathered[1] + self.last_gather[1])
         can_feat = self._reid.forward(can_u8, zero_norm=can_zn, weights=can_w)
-        return dict(B=B, N=N, K=K, P=P, L=L, order=order, n_avail=n_avail, reliable=reliable, mem_ltrb=mem_ltrb, can_ltrb=can_ltrb,
-                    mem_feat_side=mem_feat_side, can_feat=can_feat, mem_inv=mem_inv, can_inv=can_inv, select=bool(select_highest_candidate),
-                    mem_in=(mem_u8, mem_zn, mem_w), can_in=(can_u8, can_zn, can_w),      # the two BatchNorm batches themselves: an x3 pass that overflowed is run again in f32
-                    thresh=highest_candidate_minimum_thresh, keep=bool(keep_highest_value))
+        step = _Step(((mem_u8, mem_zn, mem_w), (can_u8, can_zn, can_w)), mem_inv, can_inv, B, L, P, mem_ltrb, can_ltrb)
+        return dict(step=step, N=N, K=K, order=order, n_avail=n_avail, reliable=reliable, mem_feat_side=mem_feat_side, can_feat=can_feat,
+                    select=bool(select_highest_candidate), thresh=highest_candidate_minimum_thresh, keep=bool(keep_highest_value))
 
     def _assoc_features(self, job):
         """Join the side-stream ReID batch: (mem_feat [B,L,512], can_feat [B,P,512]), the two BN batches of network.py:192-193."""
         can_feat, mem_feat = self._reid_join(job["mem_feat_side"], job["can_feat"])
-        return self._assoc_slots(job, mem_feat, can_feat)
+        return self._slots(job["step"], mem_feat, can_feat)
 
-    def _assoc_slots(self, job, mem_feat, can_feat):
+    @staticmethod
+    def _slots(step, mem_feat, can_feat):
         dev = mem_feat.device                  # features of the distinct crops -> the [B, L] / [B, P] slots they stand for
-        if len(job["mem_inv"]) != mem_feat.shape[0] or (job["mem_inv"] != np.arange(len(job["mem_inv"]))).any():
-            mem_feat = mem_feat[geometry.h2d_async(job["mem_inv"], dev)]
-        if len(job["can_inv"]) != can_feat.shape[0] or (job["can_inv"] != np.arange(len(job["can_inv"]))).any():
-            can_feat = can_feat[geometry.h2d_async(job["can_inv"], dev)]
-        return mem_feat.view(job["B"], job["L"], -1), can_feat.view(job["B"], job["P"], -1)
+        if len(step.mem_inv) != mem_feat.shape[0] or (step.mem_inv != np.arange(len(step.mem_inv))).any():
+            mem_feat = mem_feat[geometry.h2d_async(step.mem_inv, dev)]
+        if len(step.can_inv) != can_feat.shape[0] or (step.can_inv != np.arange(len(step.can_inv))).any():
+            can_feat = can_feat[geometry.h2d_async(step.can_inv, dev)]
+        return mem_feat.view(step.B, step.L, -1), can_feat.view(step.B, step.P, -1)
 
-    def _assoc_exact_reid(self, job):
-        """The two BatchNorm batches of `job` on the exact-f32 extractor (its own busca_ctx: a context holds ONE ReID weight set; created on first use) and the
-        Decision Transformer on those features - what `reid_precision="f32"` computes for the same step."""
-        if getattr(self, "_reid_exact", None) is None:
-            self._reid_exact = ReIDEncoderHIP(_lib.Context(self._device_index), self._sd, prefix=_REID_PREFIX, precision="f32")
-        self.reid_exact_reruns = getattr(self, "reid_exact_reruns", 0) + 1
-        (mu8, mzn, mw), (cu8, czn, cw) = job["mem_in"], job["can_in"]
-        mem_feat = self._reid_exact.forward(mu8, zero_norm=mzn, weights=mw)
-        can_feat = self._reid_exact.forward(cu8, zero_norm=czn, weights=cw)
-        mem_feat, can_feat = self._assoc_slots(job, mem_feat, can_feat)
-        self._ctx.set_option("dt_status", 0)            # (whatever the discarded forward on the invalid features left behind)
-        out = self._dt.forward(mem_feat, can_feat, job["mem_ltrb"], job["can_ltrb"], want_hidden=self.store_logits)
-        torch.cuda.current_stream(self._dev()).synchronize()
-        return out
-
-    def _assoc_finish(self, job, out, reid_overflow=None):
-        """network.py:403-429: probabilities -> [B, N_det (+B)] matrix (one-hot / thresholded / raw) + reliability flags.
-        `out`: dict(probs [B,P+2], argmax [B], hidden?) of this job's tracks."""
-        B, N, K, P, L = job["B"], job["N"], job["K"], job["P"], job["L"]
-        self._last = out
-        if self.store_logits and "hidden" in out:
-            pos = self._dt.can_positions(L, P)
-            self.logits = out["hidden"][:, pos]
-            self.mem_logits = out["hidden"][:, :L].mean(dim=1)
-        probs = out["probs"].cpu().numpy().astype(np.float64)                 # (synchronises the forward's stream)
-        if reid_overflow is None:
-            reid_overflow = self._reid.take_status()
-        if reid_overflow:                       # an x3 ReID pass of this step staged an activation beyond the split-fp16 range: both batches again, exact f32
-            out = self._assoc_exact_reid(job)
-            probs = out["probs"].cpu().numpy().astype(np.float64)
-        fixed = self._dt.settle(out)            # an x3 forward that clipped an operand is run again in exact float32: the tracker never gets a clipped step
-        if fixed is not out:
-            out = self._last = fixed
-            probs = out["probs"].cpu().numpy().astype(np.float64)
-            if self.store_logits and "hidden" in out:
-                self.logits = out["hidden"][:, self._dt.can_positions(L, P)]
-                self.mem_logits = out["hidden"][:, :L].mean(dim=1)
+    def _assoc_scatter(self, job, out):
+        """network.py:403-429: the SETTLED probabilities of this job's tracks (`out`: probs [B,P+2], argmax [B]) -> [B, N_det (+B)] matrix
+        (one-hot / thresholded / raw) + reliability flags."""
+        B, N, K = job["step"].B, job["N"], job["K"]
+        probs = out["probs"].cpu().numpy().astype(np.float64)
         best = out["argmax"].cpu().numpy()
         cols = N if K == 0 else N + K
         probs_matrix = np.zeros((B, cols))

@@ -4,7 +4,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import weights
+from . import geometry, weights
 
 
 PRECISIONS = {"f32": 0, "f16": 1, "x3": 2}          # BUSCA_PREC_F32 / _F16 / _F16X3 (include/busca_hip.h)
@@ -30,7 +30,7 @@ class ReIDEncoderHIP:
         self._blob = weights.reid_blob(state_dict, prefix)
         if precision == "x3":
             # a HINT only (a loose static bound: 48 sigma, summed over a layer's bottlenecks): the kernels themselves report an operand that leaves the
-            # split-fp16 range at run time (`take_status`), and busca_amd.network re-runs such a batch on the exact-f32 extractor
+            # split-fp16 range at run time (`take_status`), and BUSCA.settle re-runs such a batch on the exact-f32 extractor
             self.x3_activation_bound, self.x3_activation_bound_where = weights.x3_activation_bound(state_dict, prefix)
         want = ctx.lib.busca_reid_blob_floats()
         assert self._blob.size == want, (self._blob.size, want)
@@ -50,7 +50,7 @@ class ReIDEncoderHIP:
     def take_status(self):
         """Call once the streams of this extractor's forwards are SYNCHRONISED.  True: a split-fp16 (x3) forward since the last call staged an activation beyond
         |x| = 1023.5 (`reid_status` 2, include/busca_hip.h) - its BatchNorm statistics, hence the features of that batch, are not finite / not valid, and the caller
-        must compute the batch again on an exact-f32 extractor (BUSCA._assoc_finish does).  The status is cleared.  Always False for the f32 / f16 flavours."""
+        must compute the batch again on an exact-f32 extractor (BUSCA.settle does).  The status is cleared.  Always False for the f32 / f16 flavours."""
         if self.precision != "x3":
             return False
         st = self.ctx.get_option("reid_status")
@@ -87,10 +87,6 @@ class ReIDEncoderHIP:
             w = np.ascontiguousarray(weights, dtype=np.float32)
             assert w.shape == (n,) and (w >= 1).all()
             wsum = float(w.astype(np.float64).sum())
-            if stream is not None:      # the copy must be ordered on the stream the pass runs on
-                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-                    wd = torch.from_numpy(w).pin_memory().to(dev, non_blocking=True)
-            else:
-                wd = torch.from_numpy(w).pin_memory().to(dev, non_blocking=True)
+            wd = geometry.h2d_async(w, dev, stream)     # ordered on the stream the pass runs on
         self.ctx.check(self.ctx.lib.busca_reid_forward_w(self.ctx.h, crops_u8.data_ptr(), n, zn, _ptr(wd), wsum, feats.data_ptr(), s))
         return feats

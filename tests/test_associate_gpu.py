@@ -607,3 +607,136 @@ def test_associate_reruns_an_overflowed_x3_reid_pass_in_f32(golden_dir):
         assert m3.reid_exact_reruns == frame + 1 and m3._ctx.get_option("reid_status") == 0
     healthy.associate_embeddings(tracks, dets, dists, 11, P, True, False, extra_kalman_candidates=kals, normalize_ims=True)
     assert getattr(healthy, "reid_exact_reruns", 0) == 0 and healthy._dt.exact_reruns == 0
+
+
+# ---- BUSCA.settle: one owner for both x3 fallbacks, on every entry point ---------------------------------------------------------
+_REID = "reid_encoder.model."
+
+
+def _hot_sd(kind, seed=17):
+    """The d=64 checkpoint of `seed`, pushed out of the split-fp16 operand range: "dt" - LayerNorm weights x 3000 (the Decision Transformer clips),
+    "reid" - a BatchNorm affine x 4000 (the extractor overflows); None - as it is."""
+    sd = dict(synth.dt_state_dict(seed, d=64, ff=128))
+    rsd = dict(synth.reid_state_dict(seed))
+    if kind == "dt":
+        sd["transformer_encoder.layers.1.norm1.weight"] = sd["transformer_encoder.layers.1.norm1.weight"] * 3000.0
+    if kind == "reid":
+        rsd["layer2.0.bn1.weight"] = rsd["layer2.0.bn1.weight"] * 4000.0
+        rsd["layer2.0.bn1.bias"] = rsd["layer2.0.bn1.bias"] * 4000.0
+    sd.update({_REID + k: v for k, v in rsd.items()})
+    return sd
+
+
+def _hot_model(kind, exact=False, seed=17):
+    """x3 Decision Transformer + x3 ReID on `_hot_sd(kind)`; `exact`: the part that leaves the range in exact float32 instead - the reference to meet."""
+    from busca_amd.network import BUSCA
+    a = _args(precision="f32" if exact and kind == "dt" else "x3")
+    a.reid_precision = "f32" if exact and kind == "reid" else "x3"
+    m = BUSCA(a).to(torch.device("cuda:0")).eval()
+    m.load_state_dict(_hot_sd(kind, seed))
+    return m
+
+
+@pytest.fixture(scope="module")
+def exact_hot():
+    """kind -> the exact reference model of that hot checkpoint (seed 17), built once for the module."""
+    built = {}
+
+    def get(kind):
+        if kind not in built:
+            built[kind] = _hot_model(kind, exact=True)
+        return built[kind]
+    return get
+
+
+def _assoc(m, golden_dir, ci, via=None):
+    g = np.load(os.path.join(golden_dir, "assoc.npz"))
+    name, tracks, dets, kals, P = _case(ci)
+    return (via or m.associate_embeddings)(tracks, dets, g[name + "_dists"], 11, P, True, False, extra_kalman_candidates=kals, normalize_ims=True)
+
+
+def _forward_inputs(ci=1, L=11):
+    """Crops and ltrb boxes of one scene, stacked as BUSCA.forward takes them: [B,L,...] memories, [B,P,...] candidates (track t: detections t .. t+P-1)."""
+    name, tracks, dets, kals, P = _case(ci)
+    ltrb = lambda b: np.concatenate([b[..., :2], b[..., :2] + b[..., 2:]], -1).astype(np.float32)
+    mem = np.stack([np.stack(t.images_mem[-L:]) for t in tracks])
+    mem_box = ltrb(np.stack([np.stack(t.tlwh_mem[-L:]) * t.scale for t in tracks]))
+    can = np.stack([np.stack([d.images_mem[-1] for d in dets[t:t + P]]) for t in range(len(tracks))])
+    can_box = ltrb(np.stack([np.stack([d.tlwh_mem[-1] * d.scale for d in dets[t:t + P]]) for t in range(len(tracks))]))
+    assert mem.shape[1:] == (L, 384, 128, 3) and can.shape[:2] == (len(tracks), P)
+    return mem, can, mem_box, can_box
+
+
+def _forward_and_settle(m, inputs):
+    m(*inputs, return_logits=True)
+    torch.cuda.synchronize()
+    out = m.settle(m._last)
+    return {k: out[k].cpu().numpy() for k in ("logits", "probs", "argmax")}, m.logits.cpu().numpy(), m.mem_logits.cpu().numpy()
+
+
+@pytest.mark.parametrize("kind", ["dt", "reid"])
+def test_forward_can_be_settled(exact_hot, kind):
+    """`forward()` stays asynchronous and unsettled; a caller who synchronises and calls `model.settle(model._last)` gets both fallbacks: a clipped x3
+    Decision Transformer ("dt") or an overflowed x3 ReID pass ("reid") is computed again, and the result and the published `logits` / `mem_logits` are the
+    exact flavour's, bit for bit; the status words are cleared, so the next forward raises nothing."""
+    inputs = _forward_inputs()
+    want, want_logits, want_mem = _forward_and_settle(exact_hot(kind), inputs)
+    m = _hot_model(kind)
+    got, logits, mem_logits = _forward_and_settle(m, inputs)
+    assert np.isfinite(got["logits"]).all() and np.isfinite(logits).all()
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+    assert np.array_equal(logits, want_logits) and np.array_equal(mem_logits, want_mem)
+    assert (m._dt.exact_reruns, m.reid_exact_reruns) == ((1, 0) if kind == "dt" else (0, 1))
+    assert m._ctx.get_option("dt_status") == 0 and m._ctx.get_option("reid_status") == 0
+    again, _, _ = _forward_and_settle(m, inputs)
+    assert np.array_equal(again["logits"], want["logits"])
+
+
+def test_reloaded_weights_reach_the_exact_reid_fallback(golden_dir):
+    """The exact-f32 extractor of the ReID fallback is built from the weights of the moment: after a re-run, `load_state_dict` with other hot weights (and
+    back) gives what a reid_precision="f32" model loaded with the same weights gives, bit for bit."""
+    m, ref = _hot_model("reid"), _hot_model("reid", exact=True)
+    _assoc(m, golden_dir, 2)
+    assert m.reid_exact_reruns == 1
+    for n, seed in enumerate((18, 17)):
+        sd = _hot_sd("reid", seed)
+        m.load_state_dict(sd)
+        ref.load_state_dict(sd)
+        got, rel = _assoc(m, golden_dir, 2)
+        want, wrel = _assoc(ref, golden_dir, 2)
+        assert np.isfinite(want).all() and np.array_equal(got, want) and np.array_equal(rel, wrel), seed
+        assert m.reid_exact_reruns == 2 + n
+
+
+def test_published_state_follows_the_settled_result(exact_hot, golden_dir):
+    """store_logits: `logits` / `mem_logits` / `_last` are those of the step the tracker received - after a ReID overflow, the exact re-run's."""
+    m, ref = _hot_model("reid"), exact_hot("reid")
+    m.store_logits = ref.store_logits = True
+    try:
+        got, _ = _assoc(m, golden_dir, 2)
+        want, _ = _assoc(ref, golden_dir, 2)
+    finally:
+        ref.store_logits = False
+    assert m.reid_exact_reruns == 1 and np.array_equal(got, want)
+    assert np.array_equal(m.logits.cpu().numpy(), ref.logits.cpu().numpy())
+    assert np.array_equal(m.mem_logits.cpu().numpy(), ref.mem_logits.cpu().numpy())
+    assert np.array_equal(m._last["probs"].cpu().numpy(), ref._last["probs"].cpu().numpy())
+
+
+@pytest.mark.parametrize("kind", ["dt", "reid", None])
+def test_step_batcher_settles_a_flush_once(exact_hot, golden_dir, kind):
+    """Two steps in one flush.  A clipped merged launch is run again ONCE, as a whole; an overflowed ReID pass makes every step of the flush run again on
+    its own; every ticket is the exact model's single associate_embeddings, bit for bit.  A healthy flush re-runs nothing."""
+    from busca_amd.batcher import StepBatcher
+    m = _hot_model(kind)
+    b = StepBatcher(m)
+    tickets = [_assoc(m, golden_dir, ci, via=b.submit) for ci in (1, 2)]
+    b.flush()
+    assert b.steps == 2
+    assert m._dt.exact_reruns == (b.launches if kind == "dt" else 0) and m.reid_exact_reruns == (len(tickets) if kind == "reid" else 0)
+    if kind is not None:
+        for ci, t in zip((1, 2), tickets):
+            want, wrel = _assoc(exact_hot(kind), golden_dir, ci)
+            got, rel = t.result()
+            assert np.isfinite(want).all() and np.array_equal(got, want) and np.array_equal(rel, wrel), ci

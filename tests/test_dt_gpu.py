@@ -269,6 +269,48 @@ def test_x3_reports_operands_beyond_its_range(ctx):
     DecisionTransformerHIP(ctx, big, activation="relu", precision="f32")
 
 
+def test_x3_outputs_do_not_pin_their_inputs(ctx):
+    """What `settle` needs to run an x3 step again lives on the output itself: outputs nobody keeps (or settles) leave no inputs behind."""
+    import gc
+    from busca_amd.dt import DecisionTransformerHIP
+    m = DecisionTransformerHIP(ctx, synth.dt_state_dict(3, d=64, ff=128), precision="x3")
+    inp = synth.dt_inputs(3, 4, 11, 5)
+    fresh = lambda: [torch.from_numpy(inp[k]).cuda() for k in ("mem_feat", "can_feat", "mem_boxes", "can_boxes")]
+    for _ in range(3):
+        m.forward(*fresh())
+    gc.collect()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    for _ in range(100):
+        m.forward(*fresh())
+    gc.collect()
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == base, (torch.cuda.memory_allocated(), base)
+    assert ctx.get_option("dt_status") == 0
+
+
+def test_host_inputs_are_staged_on_the_stream_given(ctx):
+    """forward(host arrays, stream=s): the pinned asynchronous copies are ordered on `s`, where the kernels run - behind whatever `s` is still busy with -
+    and the result is the current-stream forward's, bit for bit."""
+    from busca_amd.dt import DecisionTransformerHIP
+    m = DecisionTransformerHIP(ctx, synth.dt_state_dict(3, d=64, ff=128), precision="x3")
+    inp = synth.dt_inputs(3, 4, 11, 5)
+    args = (inp["mem_feat"], inp["can_feat"], inp["mem_boxes"], inp["can_boxes"])
+    want = m.forward(*args, want_hidden=True)
+    a = torch.randn(4096, 4096, device="cuda")
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        for _ in range(4):                               # a few milliseconds of work ahead of the forward on `s`
+            busy = a @ a
+    out = m.forward(*args, want_hidden=True, stream=s.cuda_stream)
+    s.synchronize()
+    for k in ("logits", "probs", "argmax", "hidden"):
+        assert np.array_equal(out[k].cpu().numpy(), want[k].cpu().numpy()), k
+    assert ctx.get_option("dt_status") == 0
+    del busy
+
+
 def test_token_split_exchange_under_back_to_back_launches():
     """tools/dt_split_stress.py: hundreds of back-to-back forwards of changing track counts, widths and flavours (f32 / x3) on ONE context, forced and default split
     (the exchange buffers, layer-parity slots and only-growing flags are reused at once), every output bit-identical to the unsplit flavour and `dt_status` 0."""
