@@ -62,11 +62,14 @@ struct BuscaOptions {
     int dtl_attn = 1;         // BUSCA_DTL_ATTN: 1 = QKV projection + attention of a (track, head) in one kernel where it is built (0: QKV GEMM + attention kernel)
     int dt_split = -1;        // BUSCA_DT_SPLIT: token-split tail of the fused kernel (two workgroups per track): -1 = when the last round of a launch would fill at most
                               // half of the CUs, 0 = never, 1 = as many of the last tracks as fit one round (tests)
+    int dt_prune = -1;        // BUSCA_DT_PRUNE: the fused kernel's last encoder layer on the decoder's rows only (one-track unsplit f32 / x3 launches that ask for neither hidden
+                              // states nor attention maps and whose candidate rows fit one token tile less): -1 = automatic, 0 = off
     int dt_prof = 0;          // BUSCA_DT_PROF: phase stamps of the fused kernel (debug): 1 = the one-workgroup flavour, 2 = the token-split flavour (first tile's workgroup)
     int dt_exact_f32 = 0;     // 1 = a context loaded with BUSCA_PREC_F16X3 runs its forwards in exact float32 (the f32 fragment packing kept beside the split one):
                               // how the host re-runs a step whose x3 forward reported a clipped operand ("dt_status" 2)
     int crop_band = 1;        // BUSCA_CROP_BAND: 1 = crops through the LDS-staged band kernel (crop_band_kernel), 0 = one thread per output pixel (A/B, tests)
     int last_dt_grid = 0, last_dt_ntrk = 0, last_dt_split = 0;     // read-only: workgroups / tracks per workgroup / token-split tracks of the last fused launch
+    int last_dt_prune = 0;    // read-only: 1 = the one-workgroup-per-track kernel of the last fused launch ran its last layer pruned
 };
 
 struct busca_ctx {

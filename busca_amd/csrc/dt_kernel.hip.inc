@@ -498,6 +498,12 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
     constexpr int NCF = APR::nchunks(FT);   // operand chunks over a head's features
     constexpr int NCK = APR::nchunks(MT);   // operand chunks over the keys
     static_assert(FT == NTW && FTW % FSUB == 0 && KC_E % PF == 0 && KC_FFC % PF == 0, "geometry");
+    // Pruned last layer (DTParams::prune; one track per workgroup, unsplit, f32 / x3): the decoder reads only the P + nspec candidate rows, so the last layer
+    // projects K and V for every token but runs Q, the attention queries, out-proj, LayerNorm1, the FFN and LayerNorm2 on those rows alone, compacted into
+    // NQP = MT - 1 tiles (the host sets the flag only where they fit).
+    constexpr bool PRUNABLE = NTRK == 1 && !SPLIT && MT >= 2 && PREC != 1;
+    constexpr int NQP = PRUNABLE ? MT - 1 : 1;
+    static_assert(!PRUNABLE || 16 * NQP * RSP <= LD::HB_BYTES, "pruned layer: the compact residual does not fit HB");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* xop = smem + LD::OFF_XOP;
@@ -520,6 +526,7 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
     const int a = lane & 15, b = lane >> 4;
     const int L = p.L, P = p.P, T = p.T;
     const int fbase = wave * (D / 4);       // first feature this wave owns in d-wide tensors
+    const bool prune = PRUNABLE && p.prune != 0;        // (a constant false in the flavours that cannot prune: their code is what it was without it)
 
     // this wave's slice of every weight matrix (fragment (tile 0, chunk 0) + lane)
     const u32x4* w_emb = p.w_embed + (size_t)(wave * NTW) * KC_E * CW + lane;
@@ -580,7 +587,7 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
 #pragma unroll
             for (int tt = 0; tt < MTT; ++tt) X[ft][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
         gemm_stream<PREC, NTW, MTT, KC_E, PF, true, QNW, WMAX, XM>(X, wf, w_emb, KC_E * CW, hb + a * LD::RSE + b * 16, LD::RSE,
-                                                       wq_of(p.layer[0], SPLIT ? 1 : 0), KC_D * CW);
+                                                       wq_of(p.layer[0], (SPLIT || (prune && p.nlayers == 1)) ? 1 : 0), KC_D * CW);
         DT_STAMP(2);
         const float sq = sqrtf((float)D);
         const int c = p.lut_c;
@@ -635,7 +642,7 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
 
     // ---- encoder layers -------------------------------------------------------------------------------------------
 #pragma unroll 1
-    for (int l = 0; l < p.nlayers; ++l) {
+    for (int l = 0; l < p.nlayers - (prune ? 1 : 0); ++l) {        // (pruned: the last layer follows the loop)
         const DTLayerW& W = p.layer[l];
         const DTLayerW& Wn = p.layer[l + 1 < p.nlayers ? l + 1 : l];   // next layer (or a harmless re-read on the last)
         const u32x4* w_out = W.w_out + (size_t)(wave * NTW) * KC_D * CW + lane;
@@ -843,222 +850,123 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
                 }
             }
         }
-        // -- A2: S^T = K Q^T, softmax over keys, O^T = V^T P^T, all in registers -----------------------------------
-        // SPLIT: the other tiles of the track(s), in token order (this workgroup's own slot is waited for and read like the others - its values are then
-        // taken from the registers -, so that no access depends on which tile this is).  One poll covers every flag, one batch of loads every tile.
-        f32x4 kt[SPLIT ? NTRK : 1][SPLIT ? MT : 1][FT], vt[SPLIT ? NTRK : 1][SPLIT ? MT : 1][FT];
-        if constexpr (SPLIT) {
-            // Take: wave 0 waits for the flags of every tile of the track(s) and acquires at agent scope (buffer_inv sc1: this CU's L1) ONCE for the workgroup; the
-            // workgroup barrier behind it orders the other waves' loads after that acquire.  A tile's flag is raised by its workgroup's wave 0 after ALL four
-            // waves' stores (barrier + release above), so one flag per (track, tile) covers the four heads.
-            if (wave == 0) dt_xwait<MT, NTRK>(p.xflag + (size_t)xslot * MT * DT_XFLAGS, DT_XFLAGS, xstamp, p.xerr, MT * DT_XFLAGS);
-            __syncthreads();
+#define DT_NQL MTL
+#define DT_NQT MTT
+#define DT_XQ X
+#define DT_KNEXT (SPLIT || (prune && l + 2 == p.nlayers))
+#include "dt_layer_tail.hip.inc"
+#undef DT_NQL
+#undef DT_NQT
+#undef DT_XQ
+#undef DT_KNEXT
+    }
+
+    // ---- the last layer, pruned: K and V of every token, everything else on the candidate rows ----------------------------------------
+    // Compact row r < P + nspec <-> token row L + 2 r + can_pos; the rows above them replicate the last valid one and are discarded.
+    if constexpr (PRUNABLE) if (prune) {
+        // (this block's own copies of the lane coordinates, opaque to hipcc: otherwise it keeps the addresses and key indices it derives from them for the
+        // layer loop alive for this block too, and the d = 512 x3 flavour spills them)
+        int lane_ = tid & 63;
+        asm volatile("" : "+v"(lane_));
+        const int lane = lane_, a = lane & 15, b = lane >> 4;
+        f32x4 Xc[NTW][NQP];
+        const int l = p.nlayers - 1, sl = 4 + 12 * l, n = P + p.nspec;
+        const DTLayerW& W = p.layer[l];
+        const u32x4* w_out = W.w_out + (size_t)(wave * NTW) * KC_D * CW + lane;
+        // the candidate rows of the residual, as f32, to their compact places in HB (dead at a layer's start; O goes there only after they are back in registers)
 #pragma unroll
-            for (int tk = 0; tk < NTRK; ++tk) {
-                const unsigned long long* xbase = p.xch + ((size_t)(xslot + tk) * 2 + (l & 1)) * MT * 4 * XW + wave * XW;       // + tile * 4 * XW
+        for (int tt = 0; tt < MT; ++tt) {
+            const int k = 16 * tt + a - L;
+            if (k >= 0 && (k & 1) == p.can_pos && (k >> 1) < n) {
 #pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int ft = 0; ft < FT; ++ft) {
-                        const f32x4 kp = dt_xload(xbase + (size_t)i * 4 * XW + ft * 128, lane), vp = dt_xload(xbase + (size_t)i * 4 * XW + (FT + ft) * 128, lane);
-                        kt[tk][i][ft] = tile == i ? kown[tk][ft] : kp; vt[tk][i][ft] = tile == i ? vown[tk][ft] : vp;
-                    }
+                for (int ft = 0; ft < NTW; ++ft) *(f32x4*)(hb + (k >> 1) * RSP + (fbase + 16 * ft + 4 * b) * 4) = X[ft][tt];
             }
         }
-#pragma unroll
-        for (int tk = 0; tk < NTRK; ++tk) {         // attention never crosses tracks
-            constexpr int KB = SPLIT ? 0 : MT, VB = SPLIT ? 0 : 1;       // SPLIT: kf / vf hold the current track only
-            if constexpr (SPLIT) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int c = 0; c < NCF; ++c) kf[i][c] = APR::template frag<FT>(kt[tk][i], c);
-#pragma unroll
-                for (int ft = 0; ft < FT; ++ft) {
-                    f32x4 tl[MT];
-#pragma unroll
-                    for (int i = 0; i < MT; ++i) tl[i] = vt[tk][i][ft];
-#pragma unroll
-                    for (int c = 0; c < NCK; ++c) vf[0][ft][c] = APR::template frag<MT>(tl, c);
-                }
-            }
-            f32x4 S[MTL /*query tile j (of this workgroup)*/][MT /*key tile i*/];
-#pragma unroll
-            for (int j = 0; j < MTL; ++j)
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int c = 0; c < NCF; ++c) APR::mma(s, kf[tk * KB + i][c], qf[tk * MTL + j][c]);
-                    S[j][i] = s;   // lane (a,b) r : S[query 16j + a][key 16i + 4b + r]
-                }
-            DT_STAMP(sl + 3);
-#pragma unroll
-            for (int j = 0; j < MTL; ++j) {
-                float m = -INFINITY;
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (16 * i + 4 * b + r >= T) S[j][i][r] = -INFINITY;   // padded keys
-                        m = fmaxf(m, S[j][i][r]);
-                    }
-                m = xor_max_b(m);
-                float sum = 0.f;
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { const float e = PR::exp(S[j][i][r] - m); S[j][i][r] = e; sum += e; }
-                sum = xor_sum_b(sum);
-                const float inv = 1.0f / sum;
-#pragma unroll
-                for (int i = 0; i < MT; ++i) S[j][i] = S[j][i] * inv;
-            }
-            DT_STAMP(sl + 4);
-            if (p.att != nullptr) {
-#pragma unroll
-                for (int j = 0; j < MTL; ++j)
-#pragma unroll
-                    for (int i = 0; i < MT; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int q = 16 * j + a + tok0, k = 16 * i + 4 * b + r;
-                            if (q < T && k < T)
-                                p.att[((((size_t)l * p.B + track_of(tk)) * 4 + wave) * T + q) * T + k] = S[j][i][r];
-                        }
-            }
-#pragma unroll
-            for (int j = 0; j < MTL; ++j) {
-                u32x4 pf[NCK];
-#pragma unroll
-                for (int c = 0; c < NCK; ++c) pf[c] = APR::template frag<MT>(S[j], c);
-#pragma unroll
-                for (int ft = 0; ft < FT; ++ft) {
-                    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int c = 0; c < NCK; ++c) APR::mma(o, vf[tk * VB][ft][c], pf[c]);
-                    // lane (a,b) r : O[query 16j + a][feature wave*HD + 16ft + 4b + r]
-                    clipped |= PR::store4((TWO ? xop : hb) + (tk * TP1 + 16 * j + a) * LD::RSO + (wave * HD + 16 * ft + 4 * b) * EP, o, (LD::RSO - 16) / 2);
-                }
-            }
-        }
-        DT_STAMP(sl + 5);
-        __syncthreads();
-        DT_STAMP(sl + 6);
-        // -- A3: out-proj (swapped) on top of the residual, then LayerNorm1 ------------------------------------------
+        u32x4 qf[NQP][NCF], kf[MT][NCF], vf[1][FT][NCK];
+        f32x4 kown[1][FT], vown[1][FT];         // (SPLIT only)
+        const char* xl = xop + a * LD::RSX + b * 16;
+        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
         {
-            f32x4 bo[NTW], g1[NTW], be1[NTW];
-            load_vec4<NTW>(bo, W.b_out, fbase + 4 * b);
-            load_vec4<NTW>(g1, W.g1, fbase + 4 * b);
-            load_vec4<NTW>(be1, W.be1, fbase + 4 * b);
-            const int hf0 = wave * (LD::FFC / 4);
-            if constexpr (TWO) {
-                static_assert(LD::RSO == LD::RSX, "O is staged in the Xop region");
+            // K and V first, on all MT tiles (the accumulators are independent of the order; the weight stream was pointed at K by the GEMM before)
+            f32x4 acc[FT][MT];
+            f32x4 bk[FT]; float bv[FT];
+            load_vec4<FT>(bk, W.b_in, D + wave * HD + 4 * b);
 #pragma unroll
-                for (int ft = 0; ft < NTW; ++ft)
+            for (int ft = 0; ft < FT; ++ft)
 #pragma unroll
-                    for (int tt = 0; tt < MTT; ++tt) X[ft][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                gemm_stream<PREC, NTW, MTT, KC_D, PF, true, FSUB, WMAX, XM>(X, wf, w_out, KC_D * CW, xop + a * LD::RSO + b * 16, LD::RSO,
-                                                                 W.w1 + (size_t)(hf0 / 16) * KC_D * CW + lane, KC_D * CW);
-                DT_STAMP(sl + 7);
+                for (int tt = 0; tt < MT; ++tt) acc[ft][tt] = zero4;
+            gemm_stream<PREC, FT, MT, KC_D, PF, true, FT, WMAX, XM>(acc, wf, wq_of(W, 1), KC_D * CW, xl, LD::RSX, wq_of(W, 2), KC_D * CW);
+            DT_STAMP(sl + 0);
 #pragma unroll
-                for (int ft = 0; ft < NTW; ++ft)
+            for (int tt = 0; tt < MT; ++tt) {
+                f32x4 tl[FT];
 #pragma unroll
-                    for (int tt = 0; tt < MTT; ++tt)          // residual comes back from its parking place
-                        X[ft][tt] += bo[ft] + *(const f32x4*)(hb + (16 * tt + a) * RSP + (fbase + 16 * ft + 4 * b) * 4);
-            } else {
+                for (int ft = 0; ft < FT; ++ft) tl[ft] = PR::unscale(acc[ft][tt]) + bk[ft];
 #pragma unroll
-            for (int ft = 0; ft < NTW; ++ft)
-#pragma unroll
-                for (int tt = 0; tt < MTT; ++tt) X[ft][tt] = PR::prescale(X[ft][tt]);       // (x3: the residual joins the scaled accumulation; a power of two, exact)
-            gemm_stream<PREC, NTW, MTT, KC_D, PF, true, FSUB, WMAX, XM>(X, wf, w_out, KC_D * CW, hb + a * LD::RSO + b * 16, LD::RSO,
-                                                             W.w1 + (size_t)(hf0 / 16) * KC_D * CW + lane, KC_D * CW);
-            DT_STAMP(sl + 7);
-#pragma unroll
-            for (int ft = 0; ft < NTW; ++ft)
-#pragma unroll
-                for (int tt = 0; tt < MTT; ++tt) X[ft][tt] = PR::unscale(X[ft][tt]) + bo[ft];
+                for (int c = 0; c < NCF; ++c) kf[tt][c] = APR::template frag<FT>(tl, c);
             }
-            layer_norm_regs<NTW, MTT>(X, g1, be1, red1, red2, wave, a, b, invD);
-            // the two barriers inside the LayerNorm also order every wave's reads of Xop (QKV) and HB (O)
-            // before the writes below / in the FFN.
-            clipped |= store_rows<PREC, NTW, MTT>(X, xop, LD::RSX, a, b, fbase);
+#pragma unroll
+            for (int ft = 0; ft < FT; ++ft) bv[ft] = W.b_in[2 * D + wave * HD + 16 * ft + a];
+#pragma unroll
+            for (int ft = 0; ft < FT; ++ft)
+#pragma unroll
+                for (int tt = 0; tt < MT; ++tt) acc[ft][tt] = zero4;
+            gemm_stream<PREC, FT, MT, KC_D, PF, false, FT, WMAX, XM>(acc, wf, wq_of(W, 2), KC_D * CW, xl, LD::RSX, wq_of(W, 0), KC_D * CW);
+            DT_STAMP(sl + 1);
+#pragma unroll
+            for (int ft = 0; ft < FT; ++ft) {
+                f32x4 tl[MT];
+#pragma unroll
+                for (int tt = 0; tt < MT; ++tt) tl[tt] = PR::unscale(acc[ft][tt]) + bv[ft];
+#pragma unroll
+                for (int c = 0; c < NCK; ++c) vf[0][ft][c] = APR::template frag<MT>(tl, c);
+            }
         }
+        __syncthreads();                   // every wave is done reading Xop (K, V); the compact residual is visible
+#pragma unroll
+        for (int j = 0; j < NQP; ++j) {
+            const int r = 16 * j + a < n ? 16 * j + a : n - 1;
+#pragma unroll
+            for (int ft = 0; ft < NTW; ++ft) Xc[ft][j] = *(const f32x4*)(hb + r * RSP + (fbase + 16 * ft + 4 * b) * 4);
+        }
+        clipped |= store_rows<PREC, NTW, NQP>(Xc, xop, LD::RSX, a, b, fbase);     // (store4 is a function of the value alone: the operand the full layer would have read)
         __syncthreads();
-        DT_STAMP(sl + 8);
-        // -- F: FFN in NCHUNK_FF chunks of the hidden dimension, FSUB hidden tiles at a time -------------------------
-        f32x4 b2[NTW], g2[NTW], be2[NTW];
+        {
+            f32x4 acc[FT][NQP];
+            f32x4 bq[FT];
+            load_vec4<FT>(bq, W.b_in, wave * HD + 4 * b);
+#pragma unroll
+            for (int ft = 0; ft < FT; ++ft)
+#pragma unroll
+                for (int tt = 0; tt < NQP; ++tt) acc[ft][tt] = zero4;
+            gemm_stream<PREC, FT, NQP, KC_D, PF, true, NTW, WMAX, XM>(acc, wf, wq_of(W, 0), KC_D * CW, xl, LD::RSX, w_out, KC_D * CW);
+            DT_STAMP(sl + 2);
+#pragma unroll
+            for (int tt = 0; tt < NQP; ++tt) {
+                f32x4 tl[FT];
+#pragma unroll
+                for (int ft = 0; ft < FT; ++ft) tl[ft] = (PR::unscale(acc[ft][tt]) + bq[ft]) * qscale;
+#pragma unroll
+                for (int c = 0; c < NCF; ++c) qf[tt][c] = APR::template frag<FT>(tl, c);
+            }
+        }
+        const DTLayerW& Wn = W;             // (the last FFN2 prefetches a harmless re-read, as in a full last layer)
+        constexpr size_t XW = 0; const unsigned xstamp = 0;       // (SPLIT only)
+#define DT_NQL NQP
+#define DT_NQT NQP
+#define DT_XQ Xc
+#define DT_KNEXT false
+#include "dt_layer_tail.hip.inc"
+#undef DT_NQL
+#undef DT_NQT
+#undef DT_XQ
+#undef DT_KNEXT
+        // back into the first NQP tiles of X for the decoder epilogue; the last tile repeats one of them (finite, discarded), so that no register of X
+        // is live across this layer
 #pragma unroll
         for (int ft = 0; ft < NTW; ++ft)
 #pragma unroll
-            for (int tt = 0; tt < MTT; ++tt) X[ft][tt] = PR::prescale(X[ft][tt]);
-#pragma unroll
-        for (int ch = 0; ch < NCHUNK_FF; ++ch) {
-            const u32x4* w2 = W.w2 + ((size_t)(wave * NTW) * KC_FF + ch * KC_FFC) * CW + lane;
-#pragma unroll
-            for (int sb = 0; sb < NSUB; ++sb) {
-                f32x4 h[FSUB][MTT];
-                const int hloc = wave * (LD::FFC / 4) + sb * FSUB * 16;      // first hidden feature (within the chunk)
-                const int hf0 = ch * LD::FFC + hloc;
-                f32x4 b1[FSUB];
-                load_vec4<FSUB>(b1, W.b1, hf0 + 4 * b);
-#pragma unroll
-                for (int ft = 0; ft < FSUB; ++ft)
-#pragma unroll
-                    for (int tt = 0; tt < MTT; ++tt) h[ft][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                const u32x4* w1 = W.w1 + (size_t)(hf0 / 16) * KC_D * CW + lane;
-                if (sb + 1 < NSUB)
-                    gemm_stream<PREC, FSUB, MTT, KC_D, PF, true, FSUB, WMAX, XM>(h, wf, w1, KC_D * CW, xop + a * LD::RSX + b * 16, LD::RSX,
-                                                                      w1 + (size_t)FSUB * KC_D * CW, KC_D * CW);
-                else
-                    gemm_stream<PREC, FSUB, MTT, KC_D, PF, true, NTW, WMAX, XM>(h, wf, w1, KC_D * CW, xop + a * LD::RSX + b * 16, LD::RSX, w2, KC_FF * CW);
-                if (p.act == 0) {            // wave-uniform branch kept OUTSIDE the element loops (no erff for ReLU)
-#pragma unroll
-                    for (int ft = 0; ft < FSUB; ++ft)
-#pragma unroll
-                        for (int tt = 0; tt < MTT; ++tt) {
-                            f32x4 v = PR::unscale(h[ft][tt]) + b1[ft];
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                            clipped |= PR::store4(hb + (16 * tt + a) * LD::RSH + (hloc + 16 * ft + 4 * b) * EP, v, (LD::RSH - 16) / 2);
-                        }
-                } else {
-#pragma unroll
-                    for (int ft = 0; ft < FSUB; ++ft)
-#pragma unroll
-                        for (int tt = 0; tt < MTT; ++tt) {
-                            f32x4 v = PR::unscale(h[ft][tt]) + b1[ft];
-                            v = PR::gelu(v);
-                            clipped |= PR::store4(hb + (16 * tt + a) * LD::RSH + (hloc + 16 * ft + 4 * b) * EP, v, (LD::RSH - 16) / 2);
-                        }
-                }
-            }
-            __syncthreads();
-            if (ch == NCHUNK_FF - 1) DT_STAMP(sl + 9);
-            if (ch + 1 < NCHUNK_FF) {
-                const int hfn = (ch + 1) * LD::FFC + wave * (LD::FFC / 4);
-                gemm_stream<PREC, NTW, MTT, KC_FFC, PF, true, FSUB, WMAX, XM>(X, wf, w2, KC_FF * CW, hb + a * LD::RSH + b * 16, LD::RSH,
-                                                                   W.w1 + (size_t)(hfn / 16) * KC_D * CW + lane, KC_D * CW);
-                __syncthreads();           // HB is rewritten by the next chunk
-            } else {
-                // LayerNorm2's vectors are fetched here so that they are live only across the last FFN2 GEMM
-                load_vec4<NTW>(b2, W.b2, fbase + 4 * b);
-                load_vec4<NTW>(g2, W.g2, fbase + 4 * b);
-                load_vec4<NTW>(be2, W.be2, fbase + 4 * b);
-                gemm_stream<PREC, NTW, MTT, KC_FFC, PF, true, QNW, WMAX, XM>(X, wf, w2, KC_FF * CW, hb + a * LD::RSH + b * 16, LD::RSH,
-                                                                 wq_of(Wn, SPLIT ? 1 : 0), KC_D * CW);
-            }
-        }
-        DT_STAMP(sl + 10);
-#pragma unroll
-        for (int ft = 0; ft < NTW; ++ft)
-#pragma unroll
-            for (int tt = 0; tt < MTT; ++tt) X[ft][tt] = PR::unscale(X[ft][tt]) + b2[ft];
-        layer_norm_regs<NTW, MTT>(X, g2, be2, red1, red2, wave, a, b, invD);
-        clipped |= store_rows<PREC, NTW, MTT>(X, xop, LD::RSX, a, b, fbase);
-        if (TWO) park_x();                 // HB (the FFN hidden) is dead: the LayerNorm barriers are behind every wave's FFN2 reads
-        __syncthreads();
-        DT_STAMP(sl + 11);
+            for (int j = 0; j < MT; ++j) X[ft][j] = Xc[ft][j < NQP ? j : NQP - 1];
     }
 
     // ---- epilogue: optional hidden states, decoder LN + Linear(d,1), softmax, argmax ----------------------------------
@@ -1110,7 +1018,7 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
         const size_t trk_ = (size_t)tbase + wave;
         float lg = -INFINITY;
         if (lane < n) {
-            const int tg = L + 2 * lane + p.can_pos, t = wave * TP1 + tg;       // token of the track, its row in this workgroup
+            const int tg = L + 2 * lane + p.can_pos, t = prune ? lane : wave * TP1 + tg;       // token of the track, its row in this workgroup (pruned: compact)
             if (SPLIT && tg >= TP1) lg = __hip_atomic_load(p.xlg + (size_t)(xslot + wave) * MT * 16 + tg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + p.dec_bias;
             else lg = ((red1[t] + red1[TP + t]) + (red1[2 * TP + t] + red1[3 * TP + t])) + p.dec_bias;
             p.logits[trk_ * n + lane] = lg;

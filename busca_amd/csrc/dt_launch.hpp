@@ -56,6 +56,7 @@ static int dt_launch_split(busca_ctx* c, const DTParams& P0, int nsplit, hipStre
     const int nwg = ((nsplit + NTRK - 1) / NTRK) * MT;
     { int rc = dt_split_ensure(c); if (rc) return rc; }
     DTParams P = P0;
+    P.prune = 0;                // (the token-split kernel runs every layer on every row)
     P.nsingle = P.B - nsplit;
     P.xepoch = ++S.xepoch; P.xch = (unsigned long long*)S.xch; P.xflag = S.xflag; P.xlg = S.xlg; P.xerr = S.xerr_dev;
     { int rc = ensure_lds(c, (const void*)kern, LD::TOTAL); if (rc) return rc; }
@@ -70,8 +71,13 @@ static int dt_launch_split(busca_ctx* c, const DTParams& P0, int nsplit, hipStre
 }
 
 template <int PREC, int MT, int D, int FF, int NCH, int NTRK = 1>
-static int dt_launch(busca_ctx* c, const DTParams& P, hipStream_t s) {
+static int dt_launch(busca_ctx* c, const DTParams& P0, hipStream_t s) {
     typedef DTLds<PREC, MT, D, FF, 512, NCH, NTRK> LD;
+    // The one-track-per-workgroup f32 / x3 kernel runs its last layer pruned (DTParams::prune) when nothing reads the other rows of that layer - neither the hidden
+    // states nor an attention map is asked for - and the P + nspec candidate rows fit one token tile less.  Same bits: option dt_prune = 0 is for A/B and tests.
+    DTParams P = P0;
+    P.prune = (PREC != 1 && NTRK == 1 && MT >= 2 && c->opt.dt_prune != 0 && P.hidden == nullptr && P.att == nullptr && P.P + P.nspec <= 16 * (MT - 1)) ? 1 : 0;
+    c->opt.last_dt_prune = P.prune;
     static_assert(LD::TOTAL <= 160 * 1024, "LDS plan exceeds the 160 KiB of a CU");
     auto kern = dt_fused_kernel<PREC, MT, D, FF, 512, NCH, NTRK>;
     const int nwg = (P.B + NTRK - 1) / NTRK;
@@ -89,6 +95,7 @@ static int dt_launch(busca_ctx* c, const DTParams& P, hipStream_t s) {
         const int nsplit = c->opt.dt_prof == 1 ? 0 : dt_split_tracks(c, P.B, MT, PREC, PAIR, &pair);
         if (nsplit > 0) {
             c->opt.last_dt_grid = P.B - nsplit + ((nsplit + pair - 1) / pair) * MT; c->opt.last_dt_split = nsplit; c->opt.last_dt_ntrk = pair;
+            if (P.B == nsplit) c->opt.last_dt_prune = 0;        // every track took the token-split kernel
             TimedLaunch tl(c, s);
             if (P.B > nsplit) hipLaunchKernelGGL(kern, dim3(P.B - nsplit), dim3(256), LD::TOTAL, s, P);
             int rc = BUSCA_OK;

@@ -38,6 +38,8 @@ struct DTParams {
     // by one workgroup per 16-token tile; they exchange their K / V tiles per layer through xch (agent-scope stores) under the per-wave flags xflag
     int nsingle; unsigned xepoch; unsigned long long* xch; unsigned* xflag; float* xlg; int* xerr;
     int can_pos, nspec, sep_can;   // token layout (busca_dt_cfg::layout): position of the CAN token in its (SEP, CAN) pair, special candidates (NON [, BAD]), SEP encoded with the candidate's box
+    int prune;                // 1 = the last encoder layer runs its token-local half (Q, attention queries, out-proj, FFN, LayerNorms) and the decoder on the P + nspec candidate
+                              // rows only, compacted into MT - 1 tiles (last: the fields before it keep their kernel-argument offsets; set per launch by dt_launch: unsplit one-track f32 / x3 kernel, no hidden / att output)
 };
 // Phase-stamp slots per wave (BUSCA_DT_PROF): 0-3 the prologue, 4 + 12 l .. 15 + 12 l the phases of layer l, 4 + 12 DT_MAX_LAYERS the end of the kernel.
 // Sized from the layer limit (a power of two: the slot index is a shift) - with the former 64 a model of more than 4 layers stamped past the buffer.
