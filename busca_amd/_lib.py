@@ -1,4 +1,4 @@
-"""ctypes binding of libbusca_hip.so (include/busca_hip.h).  No fallback: if the library is missing the
+"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h).  No fallback: if the library is missing the
 import of any compute path raises - the product never computes on the CPU."""
 import ctypes as C
 import os
@@ -61,6 +61,12 @@ SIGNATURES = {
     "busca_bn_stats_1x1": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
 
+# include/busca_assign.h, typed after SIGNATURES (which stays the one-to-one mirror of busca_hip.h)
+ASSIGN_SIGNATURES = {
+    "busca_linear_assignment": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+ASSIGN_MAX = 2048              # BUSCA_ASSIGN_MAX
+
 _lib = None
 
 
@@ -76,7 +82,7 @@ def load():
         # runtime (same device pointers, same streams).  Loading in the other order gives two runtimes.
         import torch  # noqa: F401
         lib = C.CDLL(os.environ.get("BUSCA_HIP_LIB", LIB_PATH))      # override: experiment builds of the same ABI
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

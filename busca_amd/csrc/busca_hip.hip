@@ -30,6 +30,7 @@ static const BuscaOptionDesc BUSCA_OPTIONS[] = {
     {"BUSCA_CROP_BAND", "crop_band", &BuscaOptions::crop_band, OPT_INT}, {nullptr, "dt_exact_f32", &BuscaOptions::dt_exact_f32, OPT_FLAG},
     {nullptr, "last_dt_grid", &BuscaOptions::last_dt_grid, OPT_READONLY}, {nullptr, "last_dt_ntrk", &BuscaOptions::last_dt_ntrk, OPT_READONLY},
     {nullptr, "last_dt_split", &BuscaOptions::last_dt_split, OPT_READONLY},
+    {"BUSCA_ASSIGN_STAGE", "assign_stage", &BuscaOptions::assign_stage, OPT_INT}, {nullptr, "last_assign_staged", &BuscaOptions::last_assign_staged, OPT_READONLY},
 };
 static const BuscaOptionDesc* option_by_name(const char* name) {
     for (const BuscaOptionDesc& e : BUSCA_OPTIONS) if (e.opt && !strcmp(e.opt, name)) return &e;
@@ -40,7 +41,7 @@ static void options_from_env(BuscaOptions& o) {
         if (const char* t = e.env ? getenv(e.env) : nullptr) o.*e.field = e.kind == OPT_PRESENT ? 1 : atoi(t);
 }
 
-extern "C" int busca_version(void) { return 2000; }
+extern "C" int busca_version(void) { return 2001; }      // 2001: busca_linear_assignment (include/busca_assign.h)
 
 static std::string g_create_err;   // busca_last_error(NULL) reports why busca_ctx_create failed
 

@@ -205,3 +205,51 @@ def dt_inputs(seed, B, L=11, P=16, E=512, sentinel_every=16):
             out["can_boxes"][b, P - 1] = miss
             out["can_feat"][b, P - 1] = 0.0
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Synthetic association cost matrices (tests/golden/make_golden_assign.py, tools/assign_bench.py)
+# ----------------------------------------------------------------------------------------------
+
+def tracker_boxes(seed, n, m):
+    """float64 tlbr boxes ([n,4] tracks, [m,4] detections) of a crowded scene: the tracks scattered over a frame whose area grows
+    with the crowd (a few overlapping neighbours per box); the first min(n, m) detections are jittered copies of shuffled tracks,
+    the rest are scattered like the tracks."""
+    side = 100.0 * np.sqrt(max(n, m, 4))
+
+    def scattered(tag, k):
+        h = uniform(seed, tag + "h", (k,), 60.0, 220.0).astype(np.float64)
+        w = h * uniform(seed, tag + "a", (k,), 0.3, 0.6).astype(np.float64)
+        x = uniform(seed, tag + "x", (k,), 0.0, side).astype(np.float64)
+        y = uniform(seed, tag + "y", (k,), 0.0, side * 9 / 16).astype(np.float64)
+        return np.stack([x, y, x + w, y + h], 1)
+
+    trk = scattered("trk", n)
+    det = scattered("det", m)
+    k = min(n, m)
+    order = np.argsort(uniform(seed, "perm", (n,)), kind="stable")[:k]
+    jit = uniform(seed, "jit", (k, 4), -0.12, 0.12).astype(np.float64)
+    src = trk[order]
+    size = np.stack([src[:, 2] - src[:, 0], src[:, 3] - src[:, 1]], 1)
+    det[:k] = src + jit * np.concatenate([size, size], 1)
+    return trk, det
+
+
+def tracker_costs(seed, n, m, inf_frac=0.0):
+    """float64 [n, m] tracker-like IoU costs (1 - IoU) of tracker_boxes(seed, n, m): most entries are exactly 1 (no overlap), a
+    few per row are not.  `inf_frac`: that share of the entries becomes +inf, as a gate leaves them."""
+    trk, det = tracker_boxes(seed, n, m)
+    lt = np.maximum(trk[:, None, :2], det[None, :, :2])
+    rb = np.minimum(trk[:, None, 2:], det[None, :, 2:])
+    wh = np.clip(rb - lt, 0.0, None)
+    inter = wh[..., 0] * wh[..., 1]
+    area = lambda b: (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    cost = 1.0 - inter / (area(trk)[:, None] + area(det)[None, :] - inter)
+    if inf_frac > 0:
+        cost[uniform(seed, "gate", (n, m), 0.0, 1.0) < inf_frac] = np.inf
+    return cost
+
+
+def uniform_costs(seed, n, m, lo=0.0, hi=1.0):
+    """float64 [n, m] costs uniform in [lo, hi): the dense regime, every entry distinct with 24 random bits."""
+    return uniform(seed, "dense", (n, m), lo, hi).astype(np.float64)

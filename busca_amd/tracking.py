@@ -225,6 +225,35 @@ def fuse_motion(cost, stracks, detections, only_position=False, lambda_=0.98, ct
     return _gated(cost, stracks, detections, only_position, float(lambda_), ctx, "fuse_motion")
 
 
+def _predicted_cost_dev(ctx, stracks, detections, det_scores, fuse_motion, only_position, lambda_):
+    """The device part of an association round: predicted states, then (m > 0) their IoU cost against the detections and, with
+    `fuse_motion`, the gated blend.  -> (mean [n,8], cov [n,8,8], cost [n,m] or None, Kalman status [n] i32 or None), all device tensors."""
+    n, m = len(stracks), len(detections)
+    dev = torch.device("cuda", ctx.device)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    mean, cov = _upload_states(stracks, dev)
+    nt = torch.from_numpy(np.asarray([st.state != TRACKED for st in stracks], dtype=np.uint8)).to(dev)
+    ctx.check(ctx.lib.busca_kalman_multi_predict(ctx.h, mean.data_ptr(), cov.data_ptr(), nt.data_ptr(), n, stream))
+    cost = status = None
+    if m > 0:
+        boxes = torch.empty(n, 4, dtype=torch.float64, device=dev)
+        ctx.check(ctx.lib.busca_kalman_boxes(ctx.h, mean.data_ptr(), n, 1, boxes.data_ptr(), stream))
+        cost = geometry.pairwise(ctx, boxes, _tlbrs(detections), _lib.PAIR_IOU_COST, scores_b=det_scores)
+        if fuse_motion:
+            gate, status = _gating_dev(ctx, mean, cov, torch.from_numpy(_measurements(detections)).to(dev), only_position, 0)
+            cost = _gate_dev(cost, gate, only_position, float(lambda_))
+    return mean, cov, cost, status
+
+
+def _set_states(stracks, host):
+    """The tracks' predicted states from the leading 72 n doubles of a downloaded round."""
+    n = len(stracks)
+    pm, pc = host[:8 * n].reshape(n, 8).copy(), host[8 * n:72 * n].reshape(n, 8, 8).copy()
+    for i, st in enumerate(stracks):
+        st.mean = pm[i]
+        st.covariance = pc[i]
+
+
 def predicted_cost(stracks, detections, det_scores=None, fuse_motion=False, only_position=False, lambda_=0.98, ctx=None):
     """One association round's cost matrix without leaving the device: STrack.multi_predict (busca_kalman_multi_predict) ->
     the predicted boxes (busca_kalman_boxes, tlbr) -> iou_distance, with fuse_score when `det_scores` is given (busca_pairwise
@@ -235,32 +264,142 @@ def predicted_cost(stracks, detections, det_scores=None, fuse_motion=False, only
     if n == 0:
         return np.zeros((0, m), dtype=np.float64)
     ctx = ctx or geometry.default_context()
-    dev = torch.device("cuda", ctx.device)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    mean, cov = _upload_states(stracks, dev)
-    nt = torch.from_numpy(np.asarray([st.state != TRACKED for st in stracks], dtype=np.uint8)).to(dev)
-    ctx.check(ctx.lib.busca_kalman_multi_predict(ctx.h, mean.data_ptr(), cov.data_ptr(), nt.data_ptr(), n, stream))
+    mean, cov, cost, status = _predicted_cost_dev(ctx, stracks, detections, det_scores, fuse_motion, only_position, lambda_)
     parts = [mean.view(-1), cov.view(-1)]
     if m > 0:
-        boxes = torch.empty(n, 4, dtype=torch.float64, device=dev)
-        ctx.check(ctx.lib.busca_kalman_boxes(ctx.h, mean.data_ptr(), n, 1, boxes.data_ptr(), stream))
-        cost = geometry.pairwise(ctx, boxes, _tlbrs(detections), _lib.PAIR_IOU_COST, scores_b=det_scores)
+        parts.append(cost.view(-1))
         if fuse_motion:
-            gate, status = _gating_dev(ctx, mean, cov, torch.from_numpy(_measurements(detections)).to(dev), only_position, 0)
-            cost = _gate_dev(cost, gate, only_position, float(lambda_))
-            parts += [cost.view(-1), status.to(torch.float64)]
-        else:
-            parts.append(cost.view(-1))
+            parts.append(status.to(torch.float64))
     host = torch.cat(parts).cpu().numpy()                        # one device->host copy: states, cost matrix, status words
-    pm, pc = host[:8 * n].reshape(n, 8).copy(), host[8 * n:72 * n].reshape(n, 8, 8).copy()
-    for i, st in enumerate(stracks):
-        st.mean = pm[i]
-        st.covariance = pc[i]
+    _set_states(stracks, host)
     if m == 0:
         return np.zeros((n, 0), dtype=np.float64)
     if fuse_motion:
         _raise_flagged(host[72 * n + n * m:], "predicted_cost")
     return host[72 * n:72 * n + n * m].reshape(n, m).copy()
+
+
+# ---- linear assignment (include/busca_assign.h) ------------------------------------------------------------------------------
+def _cost_to_dev(cost, dev):
+    """A contiguous float64 device tensor of a host array or a tensor (a device float64 tensor is taken as it is)."""
+    if not torch.is_tensor(cost):
+        cost = torch.from_numpy(np.ascontiguousarray(cost, dtype=np.float64))
+    return cost.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _assign_dev(ctx, cost, batch, n, m, limit, dims=None):
+    """busca_linear_assignment on a device [batch, n, m] tensor -> device i32 [batch, n + m + 1]: per problem row_to_col, col_to_row and
+    the status word, laid out for one copy."""
+    if n > _lib.ASSIGN_MAX or m > _lib.ASSIGN_MAX:
+        raise ValueError("linear assignment of %d x %d: the device solver takes at most %d rows and columns" % (n, m, _lib.ASSIGN_MAX))
+    dev = cost.device
+    r2c = torch.empty(batch, n, dtype=torch.int32, device=dev)
+    c2r = torch.empty(batch, m, dtype=torch.int32, device=dev)
+    status = torch.zeros(batch, dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.busca_linear_assignment(ctx.h, cost.data_ptr(), batch, n, m, None if dims is None else dims.data_ptr(), float(limit),
+                                              r2c.data_ptr(), c2r.data_ptr(), None, None, status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return torch.cat([r2c, c2r, status.view(batch, 1)], 1)
+
+
+def _triple(x, y, status, what):
+    """matching.linear_assignment's return value (matching.py:44-50) of the two match vectors."""
+    if status != 0:
+        raise _lib.BuscaError("%s: the solver ran out of its loop bounds (status %d) - is a cost -inf or the limit infinite?" % (what, int(status)))
+    rows = np.nonzero(x >= 0)[0]
+    matches = np.stack([rows, x[rows]], 1).astype(int) if len(rows) else np.empty((0, 2), dtype=int)
+    return matches, np.where(x < 0)[0], np.where(y < 0)[0]
+
+
+def _empty_triple(n, m):
+    return np.empty((0, 2), dtype=int), tuple(range(n)), tuple(range(m))      # matching.py:40-41
+
+
+def linear_assignment(cost_matrix, thresh, ctx=None):
+    """matching.linear_assignment (adapters/ByteTrack/yolox/tracker/matching.py:39-50; lap.lapjv(cost, extend_cost=True, cost_limit=thresh))
+    on the GPU: the partial matching of pairs with cost < thresh that minimises the sum of (cost - thresh).  `cost_matrix`: [n,m] host
+    array or device tensor (geometry.pairwise) - a device matrix is never downloaded.  -> (matches [k,2] int sorted by row,
+    unmatched_a, unmatched_b) as ndarrays; one device->host copy of n + m + 1 ints."""
+    n, m = cost_matrix.shape
+    if n == 0 or m == 0:
+        return _empty_triple(n, m)
+    ctx = ctx or geometry.default_context()
+    out = _assign_dev(ctx, _cost_to_dev(cost_matrix, torch.device("cuda", ctx.device)), 1, n, m, thresh).cpu().numpy()[0]
+    return _triple(out[:n], out[n:n + m], out[n + m], "linear_assignment")
+
+
+def linear_assignment_batch(cost_matrices, thresh, ctx=None):
+    """linear_assignment of every matrix of a list (host arrays or device tensors, shapes may differ) in ONE launch and one copy back:
+    the matrices go into one [batch, max n, max m] slab (the padding is NaN and never read) with their sizes beside them."""
+    shapes = [tuple(c.shape) for c in cost_matrices]
+    if not shapes:
+        return []
+    n, m = max(s[0] for s in shapes), max(s[1] for s in shapes)
+    if n == 0 or m == 0:
+        return [_empty_triple(*s) for s in shapes]
+    ctx = ctx or geometry.default_context()
+    dev = torch.device("cuda", ctx.device)
+    if any(torch.is_tensor(c) for c in cost_matrices):
+        slab = torch.full((len(shapes), n, m), float("nan"), dtype=torch.float64, device=dev)
+        for k, c in enumerate(cost_matrices):
+            slab[k, :shapes[k][0], :shapes[k][1]] = _cost_to_dev(c, dev)
+    else:
+        host = np.full((len(shapes), n, m), np.nan, dtype=np.float64)
+        for k, c in enumerate(cost_matrices):
+            host[k, :shapes[k][0], :shapes[k][1]] = c
+        slab = torch.from_numpy(host).to(dev)                                  # one upload
+    dims = torch.from_numpy(np.asarray(shapes, dtype=np.int32).reshape(-1, 2)).to(dev)
+    out = _assign_dev(ctx, slab, len(shapes), n, m, thresh, dims).cpu().numpy()
+    res = []
+    for k, (nk, mk) in enumerate(shapes):
+        res.append(_empty_triple(nk, mk) if nk == 0 or mk == 0 else
+                   _triple(out[k, :nk], out[k, n:n + mk], out[k, n + m], "linear_assignment_batch[%d]" % k))
+    return res
+
+
+def min_cost_matching(distance_metric, max_distance, tracks, detections, track_indices=None, detection_indices=None, ctx=None):
+    """min_cost_matching (adapters/StrongSORT/deep_sort/linear_assignment.py:15-85) with the solver on the GPU: the metric's matrix (host
+    array or device tensor) is clamped on the device (> max_distance becomes max_distance + 1e-5, :61) and solved with that value as the
+    limit, so a clamped pair is never matched - the pairs the reference drops afterwards (:80-82).  -> (matches [(track_idx,
+    detection_idx)], unmatched_tracks, unmatched_detections) as lists."""
+    if track_indices is None:
+        track_indices = np.arange(len(tracks))
+    if detection_indices is None:
+        detection_indices = np.arange(len(detections))
+    if len(detection_indices) == 0 or len(track_indices) == 0:
+        return [], track_indices, detection_indices  # Nothing to match.
+    ctx = ctx or geometry.default_context()
+    cost = _cost_to_dev(distance_metric(tracks, detections, track_indices, detection_indices), torch.device("cuda", ctx.device))
+    n, m = cost.shape
+    limit = max_distance + 1e-5
+    cost = torch.where(cost > max_distance, limit, cost)
+    out = _assign_dev(ctx, cost, 1, n, m, limit).cpu().numpy()[0]
+    pairs, ua, ub = _triple(out[:n], out[n:n + m], out[n + m], "min_cost_matching")
+    return ([(track_indices[r], detection_indices[c]) for r, c in pairs], [track_indices[r] for r in ua], [detection_indices[c] for c in ub])
+
+
+def associate_round(stracks, detections, thresh, det_scores=None, fuse_motion=False, only_position=False, lambda_=0.98, ctx=None):
+    """One whole association round on the device: predicted_cost's chain (prediction, predicted boxes, IoU cost with fuse_score, with
+    `fuse_motion` the gated blend) followed by linear_assignment(cost, thresh).  The tracks get their predicted `mean` / `covariance`;
+    -> (matches, u_track, u_detection) as linear_assignment returns them.  One device->host copy carries the states, the two match
+    vectors and the status words; the [n,m] matrix never crosses.  Raises LinAlgError where predicted_cost does."""
+    n, m = len(stracks), len(detections)
+    if n == 0:
+        return _empty_triple(0, m)
+    ctx = ctx or geometry.default_context()
+    mean, cov, cost, status = _predicted_cost_dev(ctx, stracks, detections, det_scores, fuse_motion, only_position, lambda_)
+    parts = [mean.view(-1), cov.view(-1)]
+    if m > 0:
+        parts.append(_assign_dev(ctx, cost.contiguous(), 1, n, m, thresh).view(-1).to(torch.float64))
+        if fuse_motion:
+            parts.append(status.to(torch.float64))
+    host = torch.cat(parts).cpu().numpy()                        # one device->host copy: states, match vectors, status words
+    _set_states(stracks, host)
+    if m == 0:
+        return _empty_triple(n, 0)
+    if fuse_motion:
+        _raise_flagged(host[72 * n + n + m + 1:], "associate_round")
+    sol = host[72 * n:72 * n + n + m + 1].astype(np.int64)
+    return _triple(sol[:n], sol[n:n + m], sol[n + m], "associate_round")
 
 
 def remove_duplicate_stracks(stracksa, stracksb, ctx=None, thresh=0.15):
