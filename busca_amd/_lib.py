@@ -1,4 +1,4 @@
-"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h).  No fallback: if the library is missing the
+"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h, include/busca_appearance.h).  No fallback: if the library is missing the
 import of any compute path raises - the product never computes on the CPU."""
 import ctypes as C
 import os
@@ -67,6 +67,13 @@ ASSIGN_SIGNATURES = {
 }
 ASSIGN_MAX = 2048              # BUSCA_ASSIGN_MAX
 
+# include/busca_appearance.h
+APPEARANCE_SIGNATURES = {
+    "busca_appearance_cost": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+}
+APPEAR_MIN, APPEAR_MEAN, APPEAR_MAX = 0, 1, 2       # BUSCA_APPEAR_* reductions
+APPEAR_CLAMP0 = 1                                   # BUSCA_APPEAR_CLAMP0
+
 _lib = None
 
 
@@ -82,7 +89,7 @@ def load():
         # runtime (same device pointers, same streams).  Loading in the other order gives two runtimes.
         import torch  # noqa: F401
         lib = C.CDLL(os.environ.get("BUSCA_HIP_LIB", LIB_PATH))      # override: experiment builds of the same ABI
-        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + list(APPEARANCE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

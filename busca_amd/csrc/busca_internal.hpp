@@ -5,6 +5,7 @@
 //   busca_dtl_f32 / _f16 / _x3.hip  the layer-wise Decision-Transformer path
 //   busca_reid.hip     the ReID extractor (every flavour) and its C-ABI
 //   busca_assign.hip   the linear-assignment solver and its C-ABI (include/busca_assign.h)
+//   busca_appear.hip   the cosine gallery-cost kernel and its C-ABI (include/busca_appearance.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>

@@ -253,3 +253,32 @@ def tracker_costs(seed, n, m, inf_frac=0.0):
 def uniform_costs(seed, n, m, lo=0.0, hi=1.0):
     """float64 [n, m] costs uniform in [lo, hi): the dense regime, every entry distinct with 24 random bits."""
     return uniform(seed, "dense", (n, m), lo, hi).astype(np.float64)
+
+
+# ----------------------------------------------------------------------------------------------
+# Synthetic ReID features (tests/golden/make_golden_appearance.py, tools/appearance_bench.py)
+# ----------------------------------------------------------------------------------------------
+APPEARANCE_NOISE = (0.05, 0.3, 1.0, 3.0, 100.0)     # detection = track sample + noise of this std (x the sample's own): cosine costs from ~0 to ~1
+
+
+def _unit_rows(x):
+    x = x.astype(np.float64)
+    return (x / np.sqrt((x * x).sum(-1, keepdims=True))).astype(np.float32)
+
+
+def appearance_features(seed, n, m, E, budget=1, twins=False):
+    """float32 unit vectors: track samples [n, budget, E] (a track's samples are jittered copies of one vector) and detections [m, E];
+    detection j is normalise(sample 0 of track (7 j) mod n + noise) with the noise level APPEARANCE_NOISE[j mod 5].  `twins`: every odd track is a noisy copy (std 0.5) of the track before it, so that two tracks
+    compete for one detection.  No vector is zero."""
+    base = normal(seed, "trk", (n, 1, E)).astype(np.float64)
+    if twins:
+        k = n // 2
+        base[1:2 * k:2] = base[0:2 * k:2] + 0.5 * normal(seed, "twin", (k, 1, E)).astype(np.float64)
+    jit = normal(seed, "jit", (n, budget, E), 0.2).astype(np.float64)
+    jit[:, 0] = 0.0
+    trk = _unit_rows(base + jit)
+    owner = (np.arange(m) * 7) % n
+    std = np.asarray(APPEARANCE_NOISE, dtype=np.float64)[np.arange(m) % len(APPEARANCE_NOISE)]
+    det = _unit_rows(trk[owner, 0].astype(np.float64) * np.sqrt(E) + std[:, None] * normal(seed, "det", (m, E)).astype(np.float64))
+    assert (np.abs(trk).sum(-1) > 0).all() and (np.abs(det).sum(-1) > 0).all()
+    return trk, det

@@ -49,7 +49,7 @@ enum { BUSCA_PAIR_CENTER = 0, BUSCA_PAIR_CENTER_WEIGHTED = 1, BUSCA_PAIR_IOU = 2
 int busca_ctx_create(int device, busca_ctx** out);
 void busca_ctx_destroy(busca_ctx* ctx);
 const char* busca_last_error(const busca_ctx* ctx);
-/* Library/ABI version: major*1000 + minor.  2001: busca_linear_assignment, declared in busca_assign.h beside this header.  2000: busca_dt_cfg has the trailing `layout` field (36 bytes; a caller built against a
+/* Library/ABI version: major*1000 + minor.  2002: busca_appearance_cost, declared in busca_appearance.h beside this header.  2001: busca_linear_assignment, declared in busca_assign.h beside this header.  2000: busca_dt_cfg has the trailing `layout` field (36 bytes; a caller built against a
  * 1xxx header passes 32) and BUSCA_PREC_F16X3 exists.  busca_amd/_lib.py refuses a library whose major differs from the one it was written for. */
 int busca_version(void);
 /* The compiler flags this library was built with (busca_amd/build.py passes them in; bench.py records the string). */
