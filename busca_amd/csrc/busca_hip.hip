@@ -25,6 +25,7 @@ static const BuscaOptionDesc BUSCA_OPTIONS[] = {
     {"BUSCA_DT_NTRK", "dt_ntrk", &BuscaOptions::dt_ntrk, OPT_INT}, {"BUSCA_DT_TILED", "dt_tiled", &BuscaOptions::dt_tiled, OPT_PRESENT},
     {"BUSCA_DT_SPLIT", "dt_split", &BuscaOptions::dt_split, OPT_INT}, {"BUSCA_DT_PROF", nullptr, &BuscaOptions::dt_prof, OPT_INT},
     {"BUSCA_DT_PRUNE", "dt_prune", &BuscaOptions::dt_prune, OPT_INT}, {nullptr, "last_dt_prune", &BuscaOptions::last_dt_prune, OPT_READONLY},
+    {"BUSCA_DT_UNIQUE", "dt_unique", &BuscaOptions::dt_unique, OPT_INT}, {nullptr, "last_dt_unique", &BuscaOptions::last_dt_unique, OPT_READONLY},
     {"BUSCA_DTL_RT", nullptr, &BuscaOptions::dtl_rt, OPT_INT}, {"BUSCA_DTL_RT_MASK", nullptr, &BuscaOptions::dtl_rt_mask, OPT_INT},
     {"BUSCA_DTL_FFN", nullptr, &BuscaOptions::dtl_ffn, OPT_INT}, {"BUSCA_DTL_ATTN", nullptr, &BuscaOptions::dtl_attn, OPT_INT},
     {"BUSCA_CROP_BAND", "crop_band", &BuscaOptions::crop_band, OPT_INT}, {nullptr, "dt_exact_f32", &BuscaOptions::dt_exact_f32, OPT_FLAG},

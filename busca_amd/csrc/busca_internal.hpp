@@ -66,6 +66,8 @@ struct BuscaOptions {
                               // half of the CUs, 0 = never, 1 = as many of the last tracks as fit one round (tests)
     int dt_prune = -1;        // BUSCA_DT_PRUNE: the fused kernel's last encoder layer on the decoder's rows only (one-track unsplit f32 / x3 launches that ask for neither hidden
                               // states nor attention maps and whose candidate rows fit one token tile less): -1 = automatic, 0 = off
+    int dt_unique = -1;       // BUSCA_DT_UNIQUE: the fused kernel on the distinct token rows only - the P + 1 separators encoded as the reference are one row - (one-track unsplit
+                              // f32 / x3 launches, separator as reference, neither hidden states nor attention maps, T - P rows fitting one token tile less): -1 = automatic, 0 = off
     int dt_prof = 0;          // BUSCA_DT_PROF: phase stamps of the fused kernel (debug): 1 = the one-workgroup flavour, 2 = the token-split flavour (first tile's workgroup)
     int dt_exact_f32 = 0;     // 1 = a context loaded with BUSCA_PREC_F16X3 runs its forwards in exact float32 (the f32 fragment packing kept beside the split one):
                               // how the host re-runs a step whose x3 forward reported a clipped operand ("dt_status" 2)
@@ -73,6 +75,7 @@ struct BuscaOptions {
     int assign_stage = -1;    // BUSCA_ASSIGN_STAGE: -1 = busca_linear_assignment stages the cost matrix in LDS when it fits beside the solver's state, 0 = never (A/B, tests)
     int last_assign_staged = 0;   // read-only: 1 = the last busca_linear_assignment launch staged its cost matrices in LDS
     int last_dt_grid = 0, last_dt_ntrk = 0, last_dt_split = 0;    // read-only: workgroups / tracks per workgroup / token-split tracks of the last fused launch
+    int last_dt_unique = 0;   // read-only: 1 = the one-workgroup-per-track kernel of the last fused launch ran on the unique token rows (dt_fused_unique_kernel)
     int last_dt_prune = 0;    // read-only: 1 = the one-workgroup-per-track kernel of the last fused launch ran its last layer pruned
 };
 

@@ -198,17 +198,19 @@ __device__ __forceinline__ void gemm_prefetch(typename Prec<PREC>::op_t (&wf)[PF
 //     one-track f16 d = 256 flavour has them (same box: 0.102 -> 0.094 ms for 256 tracks; two tracks per workgroup, d = 512 and f32
 //     spill or lose 3-9 %).  A register-free rolling variant (tile-major MFMA order, a tile's next fragment read into the same
 //     registers right after its MFMAs) lost 3-10 % everywhere: the per-tile scheduling fences cost more than the reads they hide.
-template <int PREC, int NW, int NX, int NKC, int PF, bool W_IS_A, int NWN, int WMAX, int XM = 0>
+// XT: activation tile j starts at byte offset xt[j] from `lds` (per lane: the row each lane reads is looked up, dt_unique_kernel.hip.inc) instead of j * 16 * RS.
+template <int PREC, int NW, int NX, int NKC, int PF, bool W_IS_A, int NWN, int WMAX, int XM = 0, bool XT = false>
 __device__ __forceinline__ void gemm_stream(f32x4 (&acc)[NW][NX], typename Prec<PREC>::op_t (&wf)[PF][WMAX], const u32x4* __restrict__ w, int tstride,
-                                            const char* lds, int RS, const u32x4* __restrict__ wn, int tstride_n) {
+                                            const char* lds, int RS, const u32x4* __restrict__ wn, int tstride_n, const int* xt = nullptr) {
     static_assert(NKC % PF == 0 && NW <= WMAX && NWN <= WMAX && (XM != 1 || PF % 2 == 0), "bad streaming geometry");
     typedef Prec<PREC> PR;
     constexpr int CW = PR::CW;
     const int po = (RS - 16) / 2;          // x3: the lo plane of a row starts half way (every row stride is K * ES + 16)
     typename PR::op_t xf[XM == 1 ? 2 : 1][NX];
+    auto xrow = [&](int j) { if constexpr (XT) return xt[j]; else return j * 16 * RS; };
     if constexpr (XM == 1) {
 #pragma unroll
-        for (int j = 0; j < NX; ++j) xf[0][j] = PR::xload(lds + j * 16 * RS, po);
+        for (int j = 0; j < NX; ++j) xf[0][j] = PR::xload(lds + xrow(j), po);
     }
 #pragma unroll 1
     for (int k0 = 0; k0 < NKC; k0 += PF) {
@@ -217,11 +219,11 @@ __device__ __forceinline__ void gemm_stream(f32x4 (&acc)[NW][NX], typename Prec<
             const int kx = k0 + p + 1 < NKC ? k0 + p + 1 : NKC - 1;      // (the last chunk re-reads itself: no branch, no stray address)
             if constexpr (XM == 1) {
 #pragma unroll
-                for (int j = 0; j < NX; ++j) xf[(p + 1) & 1][j] = PR::xload(lds + j * 16 * RS + kx * 64, po);
+                for (int j = 0; j < NX; ++j) xf[(p + 1) & 1][j] = PR::xload(lds + xrow(j) + kx * 64, po);
                 __builtin_amdgcn_sched_barrier(0);
             } else {
 #pragma unroll
-                for (int j = 0; j < NX; ++j) xf[0][j] = PR::xload(lds + j * 16 * RS + (k0 + p) * 64, po);
+                for (int j = 0; j < NX; ++j) xf[0][j] = PR::xload(lds + xrow(j) + (k0 + p) * 64, po);
             }
             constexpr int XS = XM == 1 ? 1 : 0;
 #pragma unroll
@@ -1055,5 +1057,8 @@ __global__ void __launch_bounds__(256, (SPLIT && PREC == 0 && D <= 256 && NTRK =
 BUSCA_DT_AUX_INSTANCES(BUSCA_DT_AUX_DECL)
 #undef BUSCA_DT_AUX_DECL
 #endif
+
+// the "unique rows" flavour of the one-track f32 / x3 kernel (same helpers, same layer tail text)
+#include "dt_unique_kernel.hip.inc"
 
 #pragma clang fp contract(fast)

@@ -80,6 +80,16 @@ static int dt_launch(busca_ctx* c, const DTParams& P0, hipStream_t s) {
     c->opt.last_dt_prune = P.prune;
     static_assert(LD::TOTAL <= 160 * 1024, "LDS plan exceeds the 160 KiB of a CU");
     auto kern = dt_fused_kernel<PREC, MT, D, FF, 512, NCH, NTRK>;
+    size_t lds_bytes = LD::TOTAL;
+    // Unique rows (dt_unique_kernel.hip.inc): with the separator encoded as the reference the P + 1 SEP tokens of the candidate and NON pairs are one row, and the
+    // one-track f32 / x3 launch runs everything but K and V on the T - P distinct rows when they fit one token tile less and nothing reads the other rows
+    // (hidden states, attention maps).  Independent of B, of the split policy and of dt_prune.  Same bits: option dt_unique = 0 is for A/B and tests.
+    bool uniq = false;
+    if constexpr (PREC != 1 && NTRK == 1 && MT >= 2) {
+        uniq = c->opt.dt_unique != 0 && P.sep_can == 0 && P.hidden == nullptr && P.att == nullptr && P.T - P.P <= 16 * (MT - 1);
+        if (uniq) { kern = dt_fused_unique_kernel<PREC, MT, D, FF, 512, NCH>; lds_bytes = DTLds<PREC, MT - 1, D, FF, 512, NCH, 1>::TOTAL; }
+    }
+    c->opt.last_dt_unique = uniq ? 1 : 0;
     const int nwg = (P.B + NTRK - 1) / NTRK;
     c->opt.last_dt_grid = nwg; c->opt.last_dt_ntrk = NTRK; c->opt.last_dt_split = 0;
     if constexpr (MT >= 2 && MT <= DT_XMAX_MT && NTRK == 1) {
@@ -89,15 +99,15 @@ static int dt_launch(busca_ctx* c, const DTParams& P0, hipStream_t s) {
             { int rc = ensure_lds(c, (const void*)dt_fused_kernel<PREC, MT, D, FF, 512, NCH, 1, true>, DTLds<PREC, 1, D, FF, 512, NCH, 1>::TOTAL); if (rc) return rc; }
             if constexpr (PAIR) { int rc = ensure_lds(c, (const void*)dt_fused_kernel<PREC, MT, D, FF, 512, NCH, 2, true>, DTLds<PREC, 1, D, FF, 512, NCH, 2>::TOTAL); if (rc) return rc; }
         }
-        { int rc = ensure_lds(c, (const void*)kern, LD::TOTAL); if (rc) return rc; }
+        { int rc = ensure_lds(c, (const void*)kern, lds_bytes); if (rc) return rc; }
         // whole rounds of one-track workgroups, then the tail's tracks one token tile per workgroup: ONE timed region (the step batch), two launches on the stream
         int pair = 1;
         const int nsplit = c->opt.dt_prof == 1 ? 0 : dt_split_tracks(c, P.B, MT, PREC, PAIR, &pair);
         if (nsplit > 0) {
             c->opt.last_dt_grid = P.B - nsplit + ((nsplit + pair - 1) / pair) * MT; c->opt.last_dt_split = nsplit; c->opt.last_dt_ntrk = pair;
-            if (P.B == nsplit) c->opt.last_dt_prune = 0;        // every track took the token-split kernel
+            if (P.B == nsplit) { c->opt.last_dt_prune = 0; c->opt.last_dt_unique = 0; }        // every track took the token-split kernel
             TimedLaunch tl(c, s);
-            if (P.B > nsplit) hipLaunchKernelGGL(kern, dim3(P.B - nsplit), dim3(256), LD::TOTAL, s, P);
+            if (P.B > nsplit) hipLaunchKernelGGL(kern, dim3(P.B - nsplit), dim3(256), lds_bytes, s, P);
             int rc = BUSCA_OK;
             if constexpr (PAIR) { if (pair == 2) rc = dt_launch_split<PREC, MT, D, FF, NCH, 2>(c, P, nsplit, s); else rc = dt_launch_split<PREC, MT, D, FF, NCH, 1>(c, P, nsplit, s); }
             else rc = dt_launch_split<PREC, MT, D, FF, NCH, 1>(c, P, nsplit, s);
@@ -106,7 +116,7 @@ static int dt_launch(busca_ctx* c, const DTParams& P0, hipStream_t s) {
             return BUSCA_OK;
         }
     }
-    { int rc = ensure_lds(c, (const void*)kern, LD::TOTAL); if (rc) return rc; }
+    { int rc = ensure_lds(c, (const void*)kern, lds_bytes); if (rc) return rc; }
     const bool prof = c->opt.dt_prof == 1;   // debug: phase timestamps of workgroup 0
     if (prof) {
         DTParams Q = P;
@@ -114,12 +124,12 @@ static int dt_launch(busca_ctx* c, const DTParams& P0, hipStream_t s) {
         HIP_TRY(c, hipMalloc((void**)&d, 4 * DT_PROF_SLOTS * sizeof(long long)));
         HIP_TRY(c, hipMemset(d, 0, 4 * DT_PROF_SLOTS * sizeof(long long)));
         Q.prof = d;
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), LD::TOTAL, s, Q);
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds_bytes, s, Q);
         return dt_prof_report(c, d, nwg, s);
     }
     {
         TimedLaunch tl(c, s);
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), LD::TOTAL, s, P);
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds_bytes, s, P);
     }
     HIP_TRY(c, hipGetLastError());
     return BUSCA_OK;

@@ -1,9 +1,10 @@
 // One encoder layer of dt_fused_kernel from the attention on: softmax(Q K^T) V, out-proj + LayerNorm1, FFN + LayerNorm2.  Included by dt_kernel.hip.inc INSIDE the
-// kernel body, once per row-tile count: the text is the same for a full layer and for the pruned last layer (DTParams::prune), so every row sees the same
+// kernel body (and by dt_unique_kernel.hip.inc inside its own), once per row-tile count: the text is the same for a full layer, for the pruned last layer (DTParams::prune)
+// and for the layers of the unique-rows kernel, so every row sees the same
 // products in the same order whichever tile and lane hold it.  (Text inclusion rather than a generic lambda: with the lambda hipcc allocated registers
 // differently in EVERY flavour of the kernel - the f16 and d = 512 ones gained scratch; as included text the flavours that do not prune keep their instruction stream.)
 // The including scope defines
-//   DT_NQL    query / row tiles per track (MTL in a full layer, MT - 1 in the pruned layer), DT_NQT = DT_NQL * NTRK those of the workgroup,
+//   DT_NQL    query / row tiles per track (MTL in a full layer, MT - 1 in the pruned layer and in the unique-rows kernel), DT_NQT = DT_NQL * NTRK those of the workgroup,
 //   DT_XQ     the residual stream f32x4 [NTW][DT_NQT],
 //   DT_KNEXT  whether the GEMM that follows this layer in the weight stream is a K projection (SPLIT, or the pruned layer comes next) rather than a Q projection,
 // and the layer's l, sl, W, Wn, w_out, xstamp, XW, qf[DT_NQT][NCF], kf, vf (all MT key tiles), kown, vown (SPLIT).

@@ -54,7 +54,7 @@ const char* busca_last_error(const busca_ctx* ctx);
 int busca_version(void);
 /* The compiler flags this library was built with (busca_amd/build.py passes them in; bench.py records the string). */
 const char* busca_build_info(void);
-/* Options of one context.  Defaults are read from the environment ONCE, at busca_ctx_create (BUSCA_DT_NTRK, BUSCA_DT_TILED, BUSCA_DT_SPLIT, BUSCA_DT_PRUNE, BUSCA_CROP_BAND, ...);
+/* Options of one context.  Defaults are read from the environment ONCE, at busca_ctx_create (BUSCA_DT_NTRK, BUSCA_DT_TILED, BUSCA_DT_SPLIT, BUSCA_DT_PRUNE, BUSCA_DT_UNIQUE, BUSCA_CROP_BAND, ...);
  * no forward reads the environment.  Unknown name: BUSCA_EINVAL.
  *   "dt_ntrk"       0 auto / 1 / 2 tracks per workgroup of the f16 fused kernel (busca_amd.batcher pins it so that merged launches keep each step's flavour)
  *   "dt_tiled"      1 = force the layer-wise Decision-Transformer path (tests)
@@ -62,6 +62,9 @@ const char* busca_build_info(void);
  *                   pays (f32 / x3), 0 = never, 1 / 2 = every track that fits, one / two tracks per workgroup (tests)
  *   "dt_prune"      the fused kernel's last encoder layer on the decoder's rows only (one-track-per-workgroup f32 / x3 launches that ask for neither hidden states
  *                   nor attention maps, candidate rows fitting one token tile less; bit-identical results): -1 = automatic, 0 = off (BUSCA_DT_PRUNE; A/B, tests)
+ *   "dt_unique"     the fused kernel on the distinct token rows only: with the separators encoded as the reference the P + 1 SEP tokens of the candidate and NON pairs are
+ *                   one row (one-track-per-workgroup f32 / x3 launches that ask for neither hidden states nor attention maps, T - P rows fitting one token tile less;
+ *                   bit-identical results): -1 = automatic, 0 = off (BUSCA_DT_UNIQUE; A/B, tests)
  *   "dt_exact_f32"  1 = a context loaded with BUSCA_PREC_F16X3 runs its forwards in exact float32 on the f32 packing it keeps of the same weights (how the
  *                   host re-runs a step whose x3 forward reported a clipped operand)
  *   "dt_status"     get: 0 ok, 1 = a token-split launch lost a partner workgroup, 2 = a BUSCA_PREC_F16X3 forward had to clip an operand beyond |x| = 1023.5 -
@@ -70,7 +73,7 @@ const char* busca_build_info(void);
  *                   non-finite BatchNorm statistics; nothing is clipped silently) - valid once the forwards' streams are synchronised; set 0 clears
  *   "crop_band"     1 = crops through the LDS-staged band kernel, 0 = one thread per output pixel (tests compare the two)
  *   get only: "last_dt_grid" / "last_dt_ntrk" / "last_dt_split" (workgroups, tracks per workgroup, token-split tracks of the last fused launch),
- *             "last_dt_prune" (1 = its one-track-per-workgroup kernel ran the last layer pruned).
+ *             "last_dt_prune" (1 = its one-track-per-workgroup kernel ran the last layer pruned), "last_dt_unique" (1 = that kernel ran on the unique token rows).
  * "reid_*": ReID schedule switches of a LOADED extractor that tests flip between two forwards (set: BUSCA_ENOWEIGHTS before weights are loaded; flags read
  * back as 0 / 1).  The list of record - option names, the BUSCA_REID_* environment variables busca_reid_load_weights reads (every knob has one; a reload starts
  * again from defaults + environment), defaults and meanings - is the table REID_KNOBS in busca_amd/csrc/reid_state.hip.inc; the names above: BUSCA_OPTIONS in
