@@ -6,6 +6,7 @@
 //   busca_reid.hip     the ReID extractor (every flavour) and its C-ABI
 //   busca_assign.hip   the linear-assignment solver and its C-ABI (include/busca_assign.h)
 //   busca_appear.hip   the cosine gallery-cost kernel and its C-ABI (include/busca_appearance.h)
+//   busca_ghost.hip    GHOST's proxy distances, proxies, thresholds and mask / blend pass and their C-ABI (include/busca_ghost.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>

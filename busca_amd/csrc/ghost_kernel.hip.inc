@@ -1,0 +1,242 @@
+// GHOST association (include/busca_ghost.h): proxy distances with the two reductions busca_appearance_cost lacks, one proxy vector per track,
+// data-driven thresholds, and the mask / blend / threshold pass.  Four kernels:
+//
+//   ghost_distance_kernel   the gallery flavour of appear_kernel (appear_kernel.hip.inc) with its tile code: appear_tile / appear_diag / appear_dist give
+//                           every (sample, detection) pair the bits busca_appearance_cost gives it, and the running min / max / sum are folded in the same
+//                           order, so MIN / MEAN / MAX are that entry point's output bit for bit.  MIDRANGE = (max + min) / 2 of the two registers.  MEDIAN
+//                           (template flag, the only flavour with LDS) also stages the distances as [count][64] float64 and selects by rank: the lanes
+//                           (a, b = 0..3) of a detection column share its rows (row = b mod 4), each ranks its rows under the strict order (value, row)
+//                           against all rows, and the two rows of rank (count - 1) / 2 and count / 2 are the median's operands.  Ranks under a strict
+//                           order are a permutation, so exactly one row has each rank: no atomics, no ties, the same bits every run.
+//   ghost_proxies_kernel    one workgroup per track, thread = feature (coalesced over E), rows walked in chronological order from the ring's newest
+//   ghost_thresholds_kernel one workgroup, two passes (mean, then squared deviations) per group of rows, every sum in a fixed order
+//   ghost_combine_kernel    one thread per matrix entry
+// No multiply-add contraction anywhere: every formula is written out.
+#pragma clang fp contract(off)
+
+#define GHOST_SEL_CHUNK 8       // rows a lane ranks at a time: one LDS read of row j serves this many comparisons
+
+struct GhostDistArgs {
+    const float* gallery; const int* slot; const int* count; const float* dets; double* out;
+    int n, budget, m, E, reduce, mt;               // mt = detection tiles per track
+};
+
+template <bool MEDIAN>
+__global__ void __launch_bounds__(64 * APPEAR_WAVES) ghost_distance_kernel(GhostDistArgs p) {
+    extern __shared__ double ghost_lds[];           // MEDIAN: [budget][64] staged distances, then [2][64] the selected pair
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, a = lane & 15, b = lane >> 4;
+    const int tm = blockIdx.x % p.mt, ti = blockIdx.x / p.mt;
+    const int col = wave * 16 + a;                                        // this lane's column of the 64-detection tile
+    const int j = tm * APPEAR_TILE_M + col;
+    const float* brow = j < p.m ? p.dets + (size_t)j * p.E : nullptr;
+    const int s = p.slot ? p.slot[ti] : ti;
+    int cnt = s < 0 ? 0 : (p.count ? p.count[s] : p.budget);
+    cnt = cnt < 0 ? 0 : cnt > p.budget ? p.budget : cnt;
+    const double inf = __builtin_huge_val();
+    double mn = inf, mx = -inf, sum = 0.0, nb = 0.0;
+    ap_f64x4 dot, ga, gb;
+    const float* base = p.gallery + (size_t)(s < 0 ? 0 : s) * p.budget * p.E;
+    for (int t0 = 0; t0 < cnt; t0 += 16) {                                // the loop of appear_kernel<true>, rows beyond the count never loaded
+        const float* arow = t0 + a < cnt ? base + (size_t)(t0 + a) * p.E : nullptr;
+        if (t0 == 0) {
+            appear_tile<true>(arow, brow, p.E, b, dot, ga, gb);
+            nb = __shfl(appear_diag(gb, a), a + 16 * (a & 3));
+        } else {
+            appear_tile<false>(arow, brow, p.E, b, dot, ga, gb);
+        }
+        const double da = appear_diag(ga, a);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = b + 4 * r;
+            const double na = __shfl(da, row + 16 * b);
+            const double c = appear_dist(dot[r], na, nb, 0);
+            if (t0 + row < cnt) {
+                mn = appear_fold(mn, c, BUSCA_APPEAR_MIN);
+                mx = appear_fold(mx, c, BUSCA_APPEAR_MAX);
+                sum = appear_fold(sum, c, BUSCA_APPEAR_MEAN);
+                if (MEDIAN) ghost_lds[(size_t)(t0 + row) * APPEAR_TILE_M + col] = c;
+            }
+        }
+    }
+    mn = appear_fold(mn, __shfl_xor(mn, 16), BUSCA_APPEAR_MIN);
+    mn = appear_fold(mn, __shfl_xor(mn, 32), BUSCA_APPEAR_MIN);
+    mx = appear_fold(mx, __shfl_xor(mx, 16), BUSCA_APPEAR_MAX);
+    mx = appear_fold(mx, __shfl_xor(mx, 32), BUSCA_APPEAR_MAX);
+    sum = appear_fold(sum, __shfl_xor(sum, 16), BUSCA_APPEAR_MEAN);
+    sum = appear_fold(sum, __shfl_xor(sum, 32), BUSCA_APPEAR_MEAN);
+    double res;
+    if (cnt == 0) res = inf;
+    else if (p.reduce == BUSCA_GHOST_MIN) res = mn;
+    else if (p.reduce == BUSCA_GHOST_MAX) res = mx;
+    else if (p.reduce == BUSCA_GHOST_MEAN) res = sum / (double)cnt;
+    else res = (mx + mn) / 2.0;                                           // MIDRANGE; a NaN among the distances is in both
+    if constexpr (MEDIAN) {
+        double* sel = ghost_lds + (size_t)p.budget * APPEAR_TILE_M;       // [2][64]: the rows of rank (cnt - 1) / 2 and cnt / 2
+        __syncthreads();                                                   // cnt is the workgroup's: every wave takes the same path
+        if (cnt > 0 && mn == mn) {                                        // no NaN in this column (mn keeps one): the order is total
+            const int klo = (cnt - 1) >> 1, khi = cnt >> 1;
+            const double* v = ghost_lds + col;
+            for (int i0 = b; i0 < cnt; i0 += 4 * GHOST_SEL_CHUNK) {
+                double vi[GHOST_SEL_CHUNK];
+                int rank[GHOST_SEL_CHUNK];
+#pragma unroll
+                for (int u = 0; u < GHOST_SEL_CHUNK; ++u) {
+                    const int i = i0 + 4 * u;
+                    vi[u] = i < cnt ? v[(size_t)i * APPEAR_TILE_M] : inf;
+                    rank[u] = 0;
+                }
+                for (int jr = 0; jr < cnt; ++jr) {
+                    const double vj = v[(size_t)jr * APPEAR_TILE_M];
+#pragma unroll
+                    for (int u = 0; u < GHOST_SEL_CHUNK; ++u)
+                        rank[u] += (vj < vi[u] || (vj == vi[u] && jr < i0 + 4 * u)) ? 1 : 0;
+                }
+#pragma unroll
+                for (int u = 0; u < GHOST_SEL_CHUNK; ++u) {
+                    if (i0 + 4 * u < cnt) {
+                        if (rank[u] == klo) sel[col] = vi[u];
+                        if (rank[u] == khi) sel[APPEAR_TILE_M + col] = vi[u];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (cnt > 0) res = mn != mn ? mn : (cnt & 1) ? sel[col] : (sel[col] + sel[APPEAR_TILE_M + col]) / 2.0;
+    }
+    if (b == 0 && j < p.m) p.out[(size_t)ti * p.m + j] = res;
+}
+
+// ---- proxies ---------------------------------------------------------------------------------------------------------------------
+#define GHOST_PROXY_THREADS 256
+
+struct GhostProxyArgs {
+    const float* gallery; const int* slot; const int* count; const int* newest; float* out;
+    int n, budget, E, mode, window;
+};
+
+// chronological row k (0 = oldest of the window) of a ring whose newest row is `nw`: w rows back from it, modulo the budget
+__device__ __forceinline__ int ghost_ring_row(int nw, int w, int k, int budget) {
+    int r = (nw - (w - 1) + k) % budget;
+    return r < 0 ? r + budget : r;
+}
+
+__global__ void __launch_bounds__(GHOST_PROXY_THREADS) ghost_proxies_kernel(GhostProxyArgs p) {
+    __shared__ double part[GHOST_PROXY_THREADS / 64];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int s = p.slot ? p.slot[i] : i;
+    int cnt = s < 0 ? 0 : (p.count ? p.count[s] : p.budget);
+    cnt = cnt < 0 ? 0 : cnt > p.budget ? p.budget : cnt;
+    float* out = p.out + (size_t)i * p.E;
+    if (cnt == 0) {                                                       // a track without samples: NaN, never admissible downstream
+        for (int e = tid; e < p.E; e += GHOST_PROXY_THREADS) out[e] = __builtin_nanf("");
+        return;
+    }
+    int nw = p.newest ? p.newest[s] : cnt - 1;
+    if (nw < 0 || nw >= p.budget) nw = cnt - 1;
+    const int w = (p.window <= 0 || p.window > cnt) ? cnt : p.window;
+    const float* base = p.gallery + (size_t)s * p.budget * p.E;
+    if (p.mode == BUSCA_GHOST_PROXY_LAST || p.mode == BUSCA_GHOST_PROXY_FIRST) {
+        const float* row = base + (size_t)(p.mode == BUSCA_GHOST_PROXY_LAST ? nw : ghost_ring_row(nw, cnt, 0, p.budget)) * p.E;
+        for (int e = tid; e < p.E; e += GHOST_PROXY_THREADS) out[e] = row[e];
+    } else if (p.mode == BUSCA_GHOST_PROXY_MEDIAN) {
+        const int k = (w - 1) >> 1;                                       // the lower median, as torch.median returns
+        for (int e = tid; e < p.E; e += GHOST_PROXY_THREADS) {
+            float res = 0.f;
+            bool nan = false;
+            for (int x = 0; x < w; ++x) {                                 // a NaN among the samples is the result, as torch.median gives it
+                const float vx = base[(size_t)ghost_ring_row(nw, w, x, p.budget) * p.E + e];
+                if (vx != vx) { nan = true; res = vx; }
+            }
+            for (int x = 0; x < w && !nan; ++x) {                         // rank under the strict order (value, chronological index)
+                const float vx = base[(size_t)ghost_ring_row(nw, w, x, p.budget) * p.E + e];
+                int rank = 0;
+                for (int y = 0; y < w; ++y) {
+                    const float vy = base[(size_t)ghost_ring_row(nw, w, y, p.budget) * p.E + e];
+                    rank += (vy < vx || (vy == vx && y < x)) ? 1 : 0;
+                }
+                if (rank == k) { res = vx; break; }
+            }
+            out[e] = res;
+        }
+    } else {                                                              // MEAN, MEANNORM
+        double sq = 0.0;
+        for (int e = tid; e < p.E; e += GHOST_PROXY_THREADS) {
+            double acc = 0.0;
+            for (int x = 0; x < w; ++x) acc = acc + (double)base[(size_t)ghost_ring_row(nw, w, x, p.budget) * p.E + e];     // oldest -> newest
+            const float mean = (float)(acc / (double)w);
+            if (p.mode == BUSCA_GHOST_PROXY_MEAN) out[e] = mean;
+            else sq = sq + (double)mean * (double)mean;                    // this thread's features, ascending
+        }
+        if (p.mode == BUSCA_GHOST_PROXY_MEANNORM) {
+            for (int o = 32; o >= 1; o >>= 1) sq = sq + __shfl_xor(sq, o);
+            if ((tid & 63) == 0) part[tid >> 6] = sq;
+            __syncthreads();
+            double norm = sqrt((part[0] + part[1]) + (part[2] + part[3]));
+            if (norm < 1e-12) norm = 1e-12;                               // F.normalize's eps
+            for (int e = tid; e < p.E; e += GHOST_PROXY_THREADS) {
+                double acc = 0.0;
+                for (int x = 0; x < w; ++x) acc = acc + (double)base[(size_t)ghost_ring_row(nw, w, x, p.budget) * p.E + e];
+                const float mean = (float)(acc / (double)w);
+                out[e] = (float)((double)mean / norm);
+            }
+        }
+    }
+}
+
+// ---- thresholds --------------------------------------------------------------------------------------------------------------------
+#define GHOST_THR_THREADS 256
+
+// the sum of f(x[k]) over k = 0 .. len-1: thread t adds k = t, t + 256, ... in ascending order, the 64 lanes of a wave are added by xor-shuffles
+// (offsets 32, 16, 8, 4, 2, 1), the four waves as (w0 + w1) + (w2 + w3).  Every thread returns the total.
+template <bool SQDEV>
+__device__ __forceinline__ double ghost_block_sum(const double* x, long long len, double mean, double* part) {
+    double acc = 0.0;
+    for (long long k = threadIdx.x; k < len; k += GHOST_THR_THREADS) {
+        const double v = x[k];
+        if (SQDEV) { const double d = v - mean; acc = acc + d * d; }
+        else acc = acc + v;
+    }
+    for (int o = 32; o >= 1; o >>= 1) acc = acc + __shfl_xor(acc, o);
+    __syncthreads();                                                       // the previous sum's readers are done with `part`
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+__global__ void __launch_bounds__(GHOST_THR_THREADS) ghost_thresholds_kernel(const double* cost, long long len_act, long long len_inact, double k_act, double k_inact, double* thr) {
+    __shared__ double part[GHOST_THR_THREADS / 64];
+    for (int g = 0; g < 2; ++g) {
+        const double* x = g == 0 ? cost : cost + len_act;
+        const long long len = g == 0 ? len_act : len_inact;
+        if (len == 0) continue;                                           // no row of this kind: its threshold stays what it was
+        const double mean = ghost_block_sum<false>(x, len, 0.0, part) / (double)len;
+        const double var = ghost_block_sum<true>(x, len, mean, part) / (double)len;
+        const double kstd = (g == 0 ? k_act : k_inact) * sqrt(var);
+        if (threadIdx.x == 0) thr[g] = mean - kstd;
+    }
+}
+
+// ---- mask, blend, threshold ------------------------------------------------------------------------------------------------------
+struct GhostCombineArgs {
+    const double* app; const double* motion; const int* tlabel; const int* dlabel; const double* thr; double* out;
+    long long total; int m, num_active; double w_app, w_motion;
+};
+
+__global__ void __launch_bounds__(256) ghost_combine_kernel(GhostCombineArgs p) {
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= p.total) return;
+    const int i = (int)(k / p.m), j = (int)(k % p.m);
+    double c = p.app[k];
+    if (p.tlabel && p.tlabel[i] != p.dlabel[j]) c = __builtin_nan("");
+    if (p.motion) {
+        const double x = p.w_app * c, y = p.w_motion * p.motion[k];
+        c = x + y;
+    }
+    if (p.thr) {
+        const double t = p.thr[i < p.num_active ? 0 : 1];
+        if (!(c <= t)) c = __builtin_nan("");                              // np.where(dist <= thresh, dist, nan): a NaN threshold leaves nothing
+    }
+    p.out[k] = c;
+}
+
+#pragma clang fp contract(fast)
