@@ -88,6 +88,7 @@ def build(force=False, verbose=False):
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_assign.h"))
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_appearance.h"))
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ghost.h"))
+    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_reid_bn.h"))
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= _newest(all_deps) and (stamp_ok or not have_hipcc):
         return OUT
     if not have_hipcc:

@@ -10,6 +10,10 @@
 #include "reid_f32.hip.inc"
 #include "reid_x3.hip.inc"
 #include "reid_x3p.hip.inc"
+#pragma GCC visibility push(default)
+#include "../../include/busca_reid_bn.h"
+#pragma GCC visibility pop
+#include "reid_bn.hip.inc"
 #include "reid_state.hip.inc"
 
 ReidState* reid_state_new() { return new ReidState(); }
@@ -36,3 +40,4 @@ int reid_get_option(busca_ctx* c, const char* name, int32_t* value) {
 #include "reid_weights.hip.inc"
 #include "reid_schedule.hip.inc"
 #include "capi_reid.hip.inc"
+#include "capi_reid_bn.hip.inc"

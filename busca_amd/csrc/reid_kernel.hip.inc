@@ -800,6 +800,8 @@ __global__ void __launch_bounds__(256) reid_tail_gemv_kernel(const float* __rest
 // `flag` (split-fp16 flavour; host-mapped, else NULL): the pass's (scale, shift) table `ss` [nss] and the features are scanned for non-finite values - an
 // operand that left the fp16 range while it was staged (reid_x3.hip.inc does not clamp) makes its conv's output and BatchNorm statistics non-finite -
 // and the pass reports 2 ("reid_status") instead of returning features computed from clipped activations.
+// NORMALISE false (`output` = norm, include/busca_reid_bn.h): fc7 stays as it is; the scan is the same.
+template <bool NORMALISE>
 __global__ void __launch_bounds__(256) reid_l2norm_kernel(float* __restrict__ feats, const float* __restrict__ ss, int nss, int* flag) {
     __shared__ float sr[4];
     const int img = blockIdx.x, tid = threadIdx.x;
@@ -811,8 +813,10 @@ __global__ void __launch_bounds__(256) reid_l2norm_kernel(float* __restrict__ fe
     __syncthreads();
     const float tot = (sr[0] + sr[1]) + (sr[2] + sr[3]);
     const float nrm = fmaxf(sqrtf(tot), 1e-12f);
-    feats[(size_t)img * 512 + tid] = o0 / nrm;
-    feats[(size_t)img * 512 + tid + 256] = o1 / nrm;
+    if (NORMALISE) {
+        feats[(size_t)img * 512 + tid] = o0 / nrm;
+        feats[(size_t)img * 512 + tid + 256] = o1 / nrm;
+    }
     if (flag != nullptr) {
         bool bad = !(fabsf(tot) <= 3.0e38f);
         for (int i = img * 256 + tid; i < nss; i += gridDim.x * 256) bad = bad || !(fabsf(ss[i]) <= 3.0e38f);

@@ -95,6 +95,7 @@ static int gram_stats_launch(busca_ctx* c, const ReidPass& P, const GramConv& q)
 }
 static int reid_gram_stats(busca_ctx* c, const ReidState& R, const ReidPass& P, int idx, const _Float16* x, const float* in_ss, int H, int W) {
     const ReidConv& cv = R.convs[idx];
+    if (P.skip_stats) return BUSCA_OK;                                  // running-statistics pass: the consumers read the fixed table
     if (cv.k != 1) return fail(c, BUSCA_EINVAL, "internal: Gram statistics on a %dx%d conv", cv.k, cv.k);
     int* qt = (P.tickets != nullptr && idx < 64 && !R.k.two_launch_stats) ? P.tickets + 64 * 32 + idx * 128 : nullptr;
     return gram_stats_launch(c, P, {x, in_ss, H, W, cv.cin, cv.stride, (const _Float16*)R.d_w + cv.w_off, cv.cout, R.d_f + cv.g_off, R.d_f + cv.b_off, P.ssb + cv.ss_off, qt});
@@ -102,6 +103,7 @@ static int reid_gram_stats(busca_ctx* c, const ReidState& R, const ReidPass& P, 
 // BatchNorm (scale, shift) of conv `idx` from its per-tile statistics [gridM][2][cout]: ONE launch either way - the direct kernel
 // for few tiles, reduce + finalise-by-the-last-arriver beyond (tickets: [conv][64-channel column] words of the workspace).
 static void bn_finalize_launch(const ReidState& R, const ReidPass& P, int idx, int gridM, double invM) {
+    if (P.skip_stats) return;                                           // running-statistics pass: the per-tile partials the conv epilogues wrote stay unused
     const ReidConv& cv = R.convs[idx];
     hipStream_t s = P.s; const float* partials = P.partials; double* red = P.red; float* ss_out = P.ssb + cv.ss_off;
     const float* gamma = R.d_f + cv.g_off; const float* beta = R.d_f + cv.b_off;
@@ -201,7 +203,7 @@ static int reid_x3_conv(busca_ctx* c, const ReidState& R, const ReidPass& P, con
     const bool stem = cv.cin == 3;
     X3Args a{};
     a.in = in; a.in_ss = in_ss; a.w = R.d_wx3 + cv.wx3_off; a.inv = R.d_f + cv.inv_off; a.out = out; a.partials = P.partials; a.zero = (const float*)R.d_zero;
-    a.wts = P.wts; a.out_ss = P.ssb + cv.ss_off; a.idt = q.idt; a.idt_ss = q.idt_ss;
+    a.wts = P.wts; a.out_ss = P.rss + cv.ss_off; a.idt = q.idt; a.idt_ss = q.idt_ss;
     a.mrg_idt = mrg_idt; a.mrg_idt_ss = q.mrg_idt_ss; a.mrg_out = mrg_out;
     if (stem && K.x3_stem_halo && P.stem_crops != nullptr) { a.stem_crops = P.stem_crops; a.stem_zero = P.stem_zn; a.stem_lut = R.d_x3_lut; }
     const bool pool_out = stem && K.x3_stem_halo && P.pool_q != nullptr && mode == CONV_NORMAL;                  // the stem writes the pooled parts instead of its raw map (`out` = P)
@@ -338,7 +340,7 @@ static ConvArgs conv_args(const ReidState& R, const ReidPass& P, const ReidConv&
     g.OH = (H + 2 * cv.pad - cv.k) / cv.stride + 1; g.OW = (W + 2 * cv.pad - cv.k) / cv.stride + 1;
     g.M = P.n * g.OH * g.OW; g.wts = P.wts; g.OHWo = g.OH * g.OW;
     g.gridM = (g.M + 127) / 128; g.gridN = cv.cout == 64 ? 1 : cv.cout / 128;
-    g.out_ss = P.ssb + cv.ss_off; g.zero = (const _Float16*)R.d_zero;
+    g.out_ss = P.rss + cv.ss_off; g.zero = (const _Float16*)R.d_zero;
     return g;
 }
 
@@ -352,7 +354,7 @@ static const float* reid_f16_stem_pool(const ReidState& R, const ReidPass& P, co
     a.out = x0; a.negmask = R.stem_negmask;      // already max-pooled (min where gamma < 0): see stem_pool_kernel
     hipLaunchKernelGGL((stem_pool_kernel<2>), dim3(a.gridM), dim3(256), 0, P.s, a);
     bn_finalize_launch(R, P, 0, a.gridM, 1.0 / (P.wsum * 192.0 * 64.0));
-    return P.ssb + R.convs[0].ss_off;
+    return P.rss + R.convs[0].ss_off;
 }
 static int reid_f16_conv(busca_ctx* c, const ReidState& R, const ReidPass& P, const ConvCall<_Float16>& q, int* OHo, int* OWo) {
     const ReidKnobs& K = R.k; const ReidConv& cv = R.convs[q.idx]; hipStream_t s = P.s;
@@ -367,7 +369,7 @@ static int reid_f16_conv(busca_ctx* c, const ReidState& R, const ReidPass& P, co
         const ReidConv& dv = R.convs[q.ds_idx];
         g.ds_in = q.ds_in; g.ds_w = (const _Float16*)R.d_w + dv.w_off;
         g.ds_H = q.dsH; g.ds_W = q.dsW; g.ds_Cin = dv.cin; g.ds_stride = dv.stride; g.ds_in_ss = q.ds_in_ss;
-        g.idt_ss = P.ssb + dv.ss_off;
+        g.idt_ss = P.rss + dv.ss_off;
     }
     const unsigned nblocks = (unsigned)(((gridM + 7) / 8) * 8 * g.gridN);
 #ifdef BUSCA_CONV_PROBE
@@ -561,7 +563,7 @@ struct ReidBufs { T *in4, *stem, *x0, *r1, *r2, *r3, *rd, *xa, *xb; float* pool;
 template <class F>
 static int reid_stem(busca_ctx* c, const ReidState& R, const ReidPass& P, const ReidBufs<typename F::T>& B, const uint8_t* crops, const uint8_t* zero_norm, const float** x0_ss) {
     using T = typename F::T;
-    const float* ss0 = P.ssb + R.convs[0].ss_off;
+    const float* ss0 = P.rss + R.convs[0].ss_off;
     if constexpr (F::prec == BUSCA_PREC_F16) if (R.k.halo) { *x0_ss = reid_f16_stem_pool(R, P, crops, zero_norm, B.x0); return BUSCA_OK; }
     int OH, OW;
     if (P.stem_crops == nullptr) ew_preprocess(P.s, crops, zero_norm, (size_t)P.n * 384 * 128, B.in4);   // (else the stem fills its input halo from the bytes: no normalised copy of the batch)
@@ -593,9 +595,9 @@ struct ReidPending { const T* raw = nullptr; const float* ss = nullptr; const T*
 static void f16_tail_c1(const ReidState& R, const ReidPass& P, const ReidBufs<_Float16>& B, ReidBlock<_Float16>& k, bool ds) {
     hipStream_t s = P.s; const ReidConv& c3 = R.convs[k.i3]; const ReidConv& cn = R.convs[k.inext];
     TailC1Args ta{};
-    ta.in = B.r2; ta.in_ss = P.ssb + R.convs[k.i2].ss_off; ta.w3 = (const _Float16*)R.d_w + c3.w_off;
-    ta.out_ss = P.ssb + c3.ss_off; ta.idt = k.cur; ta.out = k.nxt;
-    if (ds) { ta.ds_in = k.cur; ta.ds_w = (const _Float16*)R.d_w + R.convs[k.id].w_off; ta.idt_ss = P.ssb + R.convs[k.id].ss_off; ta.ds_in_ss = k.cur_ss; }
+    ta.in = B.r2; ta.in_ss = P.rss + R.convs[k.i2].ss_off; ta.w3 = (const _Float16*)R.d_w + c3.w_off;
+    ta.out_ss = P.rss + c3.ss_off; ta.idt = k.cur; ta.out = k.nxt;
+    if (ds) { ta.ds_in = k.cur; ta.ds_w = (const _Float16*)R.d_w + R.convs[k.id].w_off; ta.idt_ss = P.rss + R.convs[k.id].ss_off; ta.ds_in_ss = k.cur_ss; }
     ta.w1pk = R.d_wpk + cn.wpk_off; ta.out2 = B.r1; ta.partials2 = P.partials; ta.M = P.n * k.h2 * k.w2;
     ta.wts = P.wts; ta.OHW = k.h2 * k.w2;
     const int li = k.li, gm = ta.M / (li == 2 ? 64 : 128);
@@ -626,7 +628,7 @@ static void f16_tail_c1(const ReidState& R, const ReidPass& P, const ReidBufs<_F
 // Tail, fp16 flavour with Gram statistics: BN3 (and the downsample's BN) statistics from Gram matrices of the 4x narrower inputs; then ONE conv3 pass
 // whose epilogue is the block tail, with the downsample conv accumulated by the same workgroup
 static int tail_f16_gram(busca_ctx* c, const ReidState& R, const ReidPass& P, const ReidBufs<_Float16>& B, ReidBlock<_Float16>& k) {
-    const float* ss2 = P.ssb + R.convs[k.i2].ss_off;
+    const float* ss2 = P.rss + R.convs[k.i2].ss_off;
     { int rc = reid_gram_stats(c, R, P, k.i3, B.r2, ss2, k.h2, k.w2); if (rc) return rc; }
     if (k.b == 0 && k.fuse_ds) { int rc = reid_gram_stats(c, R, P, k.id, k.cur, k.cur_ss, k.H, k.W); if (rc) return rc; }
     if (k.b == 0 && k.fuse_ds && k.fuse_c1) { f16_tail_c1(R, P, B, k, true); return BUSCA_OK; }
@@ -641,8 +643,8 @@ static int tail_f16_gram(busca_ctx* c, const ReidState& R, const ReidPass& P, co
 
 // Tail, fp16 flavour without Gram statistics: conv3 twice - statistics-only pass, then a pass whose epilogue is the block tail (no raw3 tensor)
 static int tail_f16_stats(busca_ctx* c, const ReidState& R, const ReidPass& P, const ReidBufs<_Float16>& B, ReidBlock<_Float16>& k) {
-    const float* ss2 = P.ssb + R.convs[k.i2].ss_off;
-    { int rc = reid_f16_conv(c, R, P, {k.i3, B.r2, ss2, k.h2, k.w2, B.r3, CONV_STATS_ONLY}, &k.h3, &k.w3); if (rc) return rc; }
+    const float* ss2 = P.rss + R.convs[k.i2].ss_off;
+    if (!P.skip_stats) { int rc = reid_f16_conv(c, R, P, {k.i3, B.r2, ss2, k.h2, k.w2, B.r3, CONV_STATS_ONLY}, &k.h3, &k.w3); if (rc) return rc; }   // (the tail pass below sets h3 / w3 too)
     if (k.fuse_c1 && k.b > 0 && R.k.fuse_c1_small && (P.n * k.h2 * k.w2) % (k.li == 2 ? 64 : 128) == 0) {
         f16_tail_c1(R, P, B, k, false);       // the tail also runs the next bottleneck's conv1 (statistics came from the pass above)
         return BUSCA_OK;
@@ -656,7 +658,7 @@ static int tail_f16_stats(busca_ctx* c, const ReidState& R, const ReidPass& P, c
 static int tail_x3_fused(busca_ctx* c, const ReidState& R, const ReidPass& P, const ReidBufs<float>& B, ReidBlock<float>& k) {
     const ReidKnobs& K = R.k; const ReidConv& c3 = R.convs[k.i3];
     const int n = P.n, h2 = k.h2, w2 = k.w2;
-    const float* ss2 = P.ssb + R.convs[k.i2].ss_off;
+    const float* ss2 = P.rss + R.convs[k.i2].ss_off;
     if (K.x3_gram && (c3.cin == 64 || c3.cin == 128) && (h2 * w2) % 128 == 0 && (size_t)n * h2 * w2 * c3.cin >= (size_t)K.x3_gram_min && c3.cout % QF_CPB == 0) {
         int rc = c3.cin == 64 ? x3_gram_stats_c<64>(c, R, P, k.i3, B.r2, ss2, h2 * w2) : x3_gram_stats_c<128>(c, R, P, k.i3, B.r2, ss2, h2 * w2);
         if (rc) return rc;
@@ -678,10 +680,10 @@ static int tail_x3_fused(busca_ctx* c, const ReidState& R, const ReidPass& P, co
 template <class F>
 static int tail_raw_merge(busca_ctx* c, const ReidState& R, const ReidPass& P, const ReidBufs<float>& B, ReidBlock<float>& k, ReidPending<float>& pend) {
     const ReidKnobs& K = R.k;
-    { int rc = F::conv(c, R, P, {k.i3, B.r2, P.ssb + R.convs[k.i2].ss_off, k.h2, k.w2, B.r3}, &k.h3, &k.w3); if (rc) return rc; }
+    { int rc = F::conv(c, R, P, {k.i3, B.r2, P.rss + R.convs[k.i2].ss_off, k.h2, k.w2, B.r3}, &k.h3, &k.w3); if (rc) return rc; }
     const int C = R.convs[k.i3].cout;
     const size_t npix = (size_t)P.n * k.h3 * k.w3;
-    const float* ss3 = P.ssb + R.convs[k.i3].ss_off; const bool last = k.i3 + 1 >= (int)R.convs.size();
+    const float* ss3 = P.rss + R.convs[k.i3].ss_off; const bool last = k.i3 + 1 >= (int)R.convs.size();
     if (F::prec == BUSCA_PREC_F16X3 && K.x3_merge_in && !last && npix * C >= (size_t)K.x3_merge_in_min && R.convs[k.inext].k == 1 && R.convs[k.inext].stride == 1 && R.convs[k.inext].cout % 256 == 0) {
         pend.raw = B.r3; pend.ss = ss3; pend.idt = k.idt; pend.idt_ss = k.ssd; pend.out = k.nxt;
     } else
@@ -690,7 +692,8 @@ static int tail_raw_merge(busca_ctx* c, const ReidState& R, const ReidPass& P, c
 }
 
 template <class F>
-static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* zero_norm, int32_t n, const float* weights, double weight_sum, float* feats, void* stream) {
+static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* zero_norm, int32_t n, const float* weights, double weight_sum, float* feats, void* stream,
+                             const ReidBnMode& bn = ReidBnMode()) {
     using T = typename F::T;
     if (n < 0) return fail(c, BUSCA_EINVAL, "negative batch");
     if (n == 0) return BUSCA_OK;
@@ -710,6 +713,9 @@ static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* 
     P.ssb = (float*)take((size_t)2 * 26560 * 4);           // (scale, shift) of every BN channel of THIS batch; right behind the tickets: ONE memset node zeroes both (the
                                                            // split-fp16 flavour's end-of-pass scan for non-finite entries must never read a stale word)
     HIP_TRY(c, hipMemsetAsync(P.tickets, 0, reid_ws::TICKET_BYTES + (size_t)2 * 26560 * 4, s));
+    // running-statistics pass (include/busca_reid_bn.h): the consumers read the extractor's fixed table.  The split-fp16 flavour keeps every statistics launch - they
+    // write the workspace table, which the end-of-pass scan reads: an operand beyond its range is reported exactly as in a batch-statistics pass (DESIGN.md K-REID)
+    P.rss = bn.running ? R.d_rss : P.ssb; P.skip_stats = bn.running && F::prec != BUSCA_PREC_F16X3;
     auto acts = [&](size_t per_crop) { return (T*)take(nn * per_crop * sizeof(T)); };
     ReidBufs<T> B;
     B.in4 = acts(reid_ws::IN4); B.stem = acts(reid_ws::STEM); B.x0 = acts(reid_ws::X0); B.r1 = acts(reid_ws::R1); B.r2 = acts(reid_ws::R2);
@@ -749,7 +755,7 @@ static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* 
             }
             else { int rc = F::conv(c, R, P, {k.i1, cur, k.cur_ss, H, W, B.r1}, &h1, &w1); if (rc) return rc; }
             // conv2
-            { int rc = F::conv(c, R, P, {k.i2, B.r1, P.ssb + R.convs[k.i1].ss_off, h1, w1, B.r2}, &k.h2, &k.w2); if (rc) return rc; }
+            { int rc = F::conv(c, R, P, {k.i2, B.r1, P.rss + R.convs[k.i1].ss_off, h1, w1, B.r2}, &k.h2, &k.w2); if (rc) return rc; }
             // downsample conv of the layer's first block, unless the fp16 tail accumulates it
             const bool gram = reid_use_gram(R, P, li, n * k.h2 * k.w2, k.h2 * k.w2);
             k.fuse_ds = gram && K.gram_mode != 2 && ((K.fuse_ds_layers >> li) & 1);
@@ -757,7 +763,7 @@ static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* 
             k.idt = cur; k.ssd = nullptr;
             if (b == 0 && !k.fuse_ds) {
                 { int rc = F::conv(c, R, P, {k.id, cur, k.cur_ss, H, W, B.rd}, &hd, &wd); if (rc) return rc; }
-                k.idt = B.rd; k.ssd = P.ssb + R.convs[k.id].ss_off;
+                k.idt = B.rd; k.ssd = P.rss + R.convs[k.id].ss_off;
             }
             // tail
             int rc;
@@ -776,7 +782,16 @@ static int reid_forward_impl(busca_ctx* c, const uint8_t* crops, const uint8_t* 
         hipLaunchKernelGGL((reid_tail_gemv_kernel<1>), dim3(n, 8), dim3(256), 0, s, (const float*)B.pool, (const float*)(R.d_f + R.red_w_off),
                            (const float*)(R.d_f + R.red_b_off), feats, n);
     // (split-fp16 flavour: the same launch scans this pass's BatchNorm (scale, shift) table and the features for non-finite values -> "reid_status")
-    hipLaunchKernelGGL(reid_l2norm_kernel, dim3(n), dim3(256), 0, s, feats, (const float*)P.ssb, 2 * 26560, F::prec == BUSCA_PREC_F16X3 ? R.xerr_dev : (int*)nullptr);
+    int* const flag = F::prec == BUSCA_PREC_F16X3 ? R.xerr_dev : (int*)nullptr;
+    if (bn.output == BUSCA_REID_OUT_NORM) hipLaunchKernelGGL(reid_l2norm_kernel<false>, dim3(n), dim3(256), 0, s, feats, (const float*)P.ssb, 2 * 26560, flag);
+    else hipLaunchKernelGGL(reid_l2norm_kernel<true>, dim3(n), dim3(256), 0, s, feats, (const float*)P.ssb, 2 * 26560, flag);
+    if (bn.momentum != 0.0) {
+        // train-mode update of the running statistics from this pass's finished table, then the fixed table again (reid_bn.hip.inc)
+        ReidBnCounts m = R.bn_counts;
+        for (int i = 0; i < REID_NCONV; ++i) m.count[i] *= (double)n;
+        hipLaunchKernelGGL(reid_bn_update_kernel, dim3((26560 + 255) / 256), dim3(256), 0, s, (const float*)P.ssb, (const float*)R.d_f, R.bn_map, m, bn.momentum, R.d_run);
+        hipLaunchKernelGGL(reid_bn_table_kernel, dim3((26560 + 255) / 256), dim3(256), 0, s, (const float*)R.d_run, (const float*)R.d_f, R.bn_map, R.d_rss);
+    }
     HIP_TRY(c, hipGetLastError());
     return BUSCA_OK;
 }

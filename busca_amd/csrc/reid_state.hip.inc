@@ -108,6 +108,12 @@ struct ReidState {
     unsigned long long stem_negmask = 0;   // bit c: the stem BatchNorm's gamma of channel c is negative (stem_pool_kernel pools it with min)
     void* d_zero = nullptr;           // 256 zero bytes: the load target of padded / out-of-range operand pieces
     int num_cu = 256;                 // compute units of the device (persistent launches: one workgroup per CU)
+    // running-statistics BatchNorm (include/busca_reid_bn.h): absent until busca_reid_load_running_stats / _reset_running_stats, dropped with the weights
+    float* d_run = nullptr;           // per conv in blob order running_mean[Cout], running_var[Cout]
+    float* d_rss = nullptr;           // the FIXED (scale, shift) table built from them, laid out as a pass's own table ([sum C][2])
+    bool run_loaded = false;
+    ReidBnMap bn_map{};               // which channels, affine parameters and output pixels per crop each conv's BatchNorm has (reid_bn.hip.inc)
+    ReidBnCounts bn_counts{};
     int* xerr = nullptr; int* xerr_dev = nullptr;    // F16X3: status word in host-mapped memory ("reid_status": 2 = a staged operand left the fp16 range in a forward since it was last cleared)
     // workspaces: one per stream that has called busca_reid_forward (the two BN batches of a step may run
     // concurrently on two streams); reused, grown on demand
@@ -124,6 +130,10 @@ struct ReidPass {
     const uint8_t* stem_crops = nullptr; const uint8_t* stem_zn = nullptr;   // F16X3 stem with byte input: the crops / padding flags
     const float* pool_p = nullptr; float* pool_q = nullptr;          // F16X3: the pooled stem parts (X3_POOL / X3_POOLIN)
     float *ssb = nullptr, *partials = nullptr; double* red = nullptr;   // (scale, shift) of every BN channel of THIS batch; per-tile statistics of the running conv, their slice sums
+    // Two tables: `ssb` (workspace) is what the statistics finalisers WRITE and reid_l2norm_kernel scans; `rss` is what every consumer of a BatchNorm READS -
+    // ssb itself in a batch-statistics pass, the extractor's fixed table (ReidState::d_rss) in a running-statistics pass.
+    const float* rss = nullptr;
+    bool skip_stats = false;                                         // running-statistics pass of the exact-f32 / fp16 flavours: nothing whose only product is statistics is launched
     float* gpart = nullptr; double* gG = nullptr; double *x3part = nullptr, *x3G = nullptr;   // Gram scratch of the fp16 (gram_stats_launch) / split-fp16 (x3_gram_stats_c) flavour
 };
 
@@ -135,6 +145,8 @@ static void reid_free(ReidState& r) {
     if (r.d_x3_lut) { hipFree(r.d_x3_lut); r.d_x3_lut = nullptr; }
     if (r.d_f) hipFree(r.d_f);
     if (r.d_ss) hipFree(r.d_ss);
+    if (r.d_run) hipFree(r.d_run);
+    if (r.d_rss) hipFree(r.d_rss);
     if (r.d_zero) hipFree(r.d_zero);
     for (auto& w : r.ws) if (w.ptr) hipFree(w.ptr);
     if (r.xerr) hipHostFree(r.xerr);

@@ -213,6 +213,25 @@ extern "C" int busca_reid_load_weights_ex(busca_ctx* c, const float* blob, size_
     HIP_TRY(c, hipMalloc(&R.d_zero, 256));
     HIP_TRY(c, hipMemset(R.d_zero, 0, 256));
     if (ss_total != (size_t)2 * 26560) return fail(c, BUSCA_EINVAL, "internal: BN channel count %zu", ss_total / 2);
+    {   // the BatchNorm map of the running-statistics kernels (reid_bn.hip.inc): channels, affine parameters, output pixels per crop of every conv in forward order
+        if ((int)R.convs.size() != REID_NCONV) return fail(c, BUSCA_EINVAL, "internal: %zu convs", R.convs.size());
+        int H = 96, W = 32, i = 1;
+        const int nblk[4] = {3, 4, 6, 3};
+        R.bn_counts.count[0] = 192.0 * 64.0;
+        for (int li = 0; li < 4; ++li)
+            for (int b = 0; b < nblk[li]; ++b) {
+                const int st = R.convs[i + 1].stride, H2 = (H - 1) / st + 1, W2 = (W - 1) / st + 1;
+                R.bn_counts.count[i++] = (double)(H * W);
+                R.bn_counts.count[i++] = (double)(H2 * W2);
+                R.bn_counts.count[i++] = (double)(H2 * W2);
+                if (b == 0) R.bn_counts.count[i++] = (double)(H2 * W2);
+                H = H2; W = W2;
+            }
+        for (int k = 0; k < REID_NCONV; ++k) {
+            R.bn_map.first[k] = (int)(R.convs[k].ss_off / 2); R.bn_map.g_off[k] = (int)R.convs[k].g_off; R.bn_map.b_off[k] = (int)R.convs[k].b_off;
+        }
+        R.bn_map.first[REID_NCONV] = REID_BN_CHANNELS;
+    }
     HIP_TRY(c, hipMemcpy(R.d_f, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
     R.loaded = true;
     return BUSCA_OK;

@@ -47,6 +47,21 @@ def memory_indices(n_hist, seq_len, use_broader_memory):
     return list(range(max(0, n_hist - seq_len), n_hist))
 
 
+def _to_u8_hwc_bgr(x, dev):
+    """Accept u8 BGR [...,384,128,3] or the reference's normalised float RGB [...,3,384,128]; the latter is
+    mapped back to the u8 crop it was made from (the normalisation is injective on 0..255)."""
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    x = x.to(dev)
+    if x.dtype == torch.uint8:
+        return x.reshape(-1, 384, 128, 3).contiguous()
+    x = x.reshape(-1, 3, 384, 128).double()
+    mean = torch.tensor(_PIX_MEAN_RGB, device=x.device).view(1, 3, 1, 1)
+    std = torch.tensor(_PIX_STD_RGB, device=x.device).view(1, 3, 1, 1)
+    u8 = torch.round((x * std + mean) * 255.0).clamp_(0, 255).to(torch.uint8)
+    return u8.flip(1).permute(0, 2, 3, 1).contiguous()          # RGB CHW -> BGR HWC
+
+
 class _ReIDFacade:
     """`model.reid_encoder`: callable like the reference's ReID_Encoder (network.py:510-575): returns
     (None, feats[n,512]); accepts u8 BGR [n,384,128,3] crops or normalised float RGB [n,3,384,128]."""
@@ -276,18 +291,7 @@ class BUSCA:
         return torch.device("cuda", self._device_index)
 
     def _to_u8_hwc_bgr(self, x):
-        """Accept u8 BGR [...,384,128,3] or the reference's normalised float RGB [...,3,384,128]; the latter is
-        mapped back to the u8 crop it was made from (the normalisation is injective on 0..255)."""
-        if not torch.is_tensor(x):
-            x = torch.from_numpy(np.ascontiguousarray(x))
-        x = x.to(self._dev())
-        if x.dtype == torch.uint8:
-            return x.reshape(-1, 384, 128, 3).contiguous()
-        x = x.reshape(-1, 3, 384, 128).double()
-        mean = torch.tensor(_PIX_MEAN_RGB, device=x.device).view(1, 3, 1, 1)
-        std = torch.tensor(_PIX_STD_RGB, device=x.device).view(1, 3, 1, 1)
-        u8 = torch.round((x * std + mean) * 255.0).clamp_(0, 255).to(torch.uint8)
-        return u8.flip(1).permute(0, 2, 3, 1).contiguous()          # RGB CHW -> BGR HWC
+        return _to_u8_hwc_bgr(x, self._dev())
 
     def _reid_features(self, x):
         self._sync()
@@ -638,5 +642,137 @@ class BUSCA:
                                         host_copy="never" if self.device_only_crops else self.crop_host_copy, output_size=output_size)
 
 
-class ReID_Encoder(_ReIDFacade):
-    """Name kept for importers of busca.network.ReID_Encoder."""
+class ReID_Encoder:
+    """The reference's standalone ReID_Encoder (busca/network.py:510-575) on the HIP extractor: same constructor, `(cls_probs, feats) = enc(x)` with
+    cls_probs None (the classifier head is not built), x u8 BGR [n,384,128,3] crops or the reference's normalised float RGB [n,3,384,128].
+
+    use_domain_adaptation=True: BatchNorm on the statistics of the batch, as `BUSCA.reid_encoder`.  False: torch's running statistics
+    (include/busca_reid_bn.h) - after `eval()` (the state a new encoder is in) a call is the eval-mode forward on them, after `train()` a call is a
+    train-mode forward that also moves them by `momentum` (default 0.1, BatchNorm2d's).  GHOST's modes are one-liners on that:
+    the default is `eval()`; `first_batch` is `train(); enc(first); eval()` with momentum 1 (`_reset`: `reset_running_stats()` before it).
+
+    pretrained_path follows load_net (busca/reid/load_trained_net.py:43-66): "no" / None keeps synth.reid_state_dict(seed) and reset running statistics;
+    a checkpoint (raw state_dict or {'model_state_dict': ...}) loses its `fc` / `fc_person` heads and is loaded strictly - a key this network does not
+    have raises; BatchNorm running statistics are read from it, `num_batches_tracked` is ignored.
+
+    precision: "x3" (default), "f32" or "f16" (ReIDEncoderHIP).  In x3 every call SYNCHRONISES the current stream once to read `reid_status` (a train-mode
+    call that moves the statistics once more, before it, to keep what they were); a batch that
+    left the split-fp16 range is computed again - forward, and update of the statistics - on an exact-f32 extractor of the same weights and statistics
+    (its own context, built on first use), counted in `exact_reruns`."""
+    PRETRAINED_SIZE = (384, 128)
+
+    def __init__(self, num_classes, device, pretrained_path=None, use_domain_adaptation=True, output_option='plain', trainable=False,
+                 use_checkpointing=True, precision=None, seed=0):
+        if trainable:
+            raise NotImplementedError("ReID_Encoder(trainable=True): the HIP extractor is inference only (no backward pass)")
+        if output_option not in ("plain", "norm", "neck"):
+            raise ValueError("output_option %r (plain / norm / neck)" % (output_option,))
+        self.num_classes = num_classes
+        self.device = device
+        self.pretrained_path = pretrained_path
+        self.use_domain_adaptation = bool(use_domain_adaptation)
+        self.output_option = output_option
+        self.trainable = False
+        self.use_checkpointing = use_checkpointing
+        self.precision = precision if precision is not None else os.environ.get("BUSCA_AMD_REID_PRECISION", "x3")
+        self.embedding_size = 512                      # int(2048 / red), red = 4
+        self.training = False
+        self.momentum = 0.1
+        self.exact_reruns = 0
+        self._device_index = BUSCA._index_of(device)
+        self._sd = OrderedDict(synth.reid_state_dict(int(seed)))
+        self._running0 = None                          # running statistics of the checkpoint (None: reset)
+        if pretrained_path is not None and pretrained_path != "no":
+            self._load_checkpoint(pretrained_path)
+        self._enc = None
+        self._exact = None
+
+    def _load_checkpoint(self, path):
+        sd = BUSCA._read_checkpoint(path)
+        sd = {k: v for k, v in sd.items() if "fc" not in k.split(".") and "fc_person" not in k.split(".")}
+        buffers = ("running_mean", "running_var", "num_batches_tracked")
+        unexpected = [k for k in sd if k not in self._sd and not (k.split(".")[-1] in buffers and ".".join(k.split(".")[:-1]) + ".weight" in self._sd)]
+        if unexpected:
+            raise RuntimeError("Error(s) in loading state_dict for ReID_Encoder from {!r}: unexpected key(s) {}{}".format(
+                path, unexpected[:8], " ..." if len(unexpected) > 8 else ""))
+        for k, v in sd.items():
+            if k in self._sd:
+                arr = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)
+                if arr.shape != self._sd[k].shape:
+                    raise RuntimeError("size mismatch for {}: {} vs {}".format(k, arr.shape, self._sd[k].shape))
+                self._sd[k] = np.ascontiguousarray(arr)
+        if any(k.split(".")[-1] in buffers[:2] for k in sd):
+            self._running0 = weights.reid_running_blob(sd)       # (a checkpoint with some of them but not all: KeyError naming the missing key)
+
+    # ---- nn.Module-like surface -----------------------------------------------------------------------------
+    def train(self, mode=True):
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def to(self, device):
+        idx = BUSCA._index_of(device)
+        if idx != self._device_index:
+            if self._enc is not None:
+                self._running0 = self._enc.running_stats()
+            self._device_index, self._enc, self._exact = idx, None, None
+        self.device = device
+        return self
+
+    def _dev(self):
+        return torch.device("cuda", self._device_index)
+
+    def _sync(self):
+        if self._enc is None:
+            self._enc = ReIDEncoderHIP(_lib.Context(self._device_index), self._sd, precision=self.precision)
+            if self._running0 is None:
+                self._enc.reset_running_stats()
+            else:
+                self._enc.load_running_stats(self._running0)
+        return self._enc
+
+    def reset_running_stats(self):
+        self._sync().reset_running_stats()
+
+    def load_running_stats(self, sd_or_blob, prefix=""):
+        self._sync().load_running_stats(sd_or_blob, prefix)
+
+    def running_stats(self):
+        return self._sync().running_stats()
+
+    # ---- forward ------------------------------------------------------------------------------------------------
+    def _run(self, enc, u8, output):
+        if self.use_domain_adaptation:
+            return enc.adapt(u8, 0.0, output)                    # batch statistics; `plain`: the bits of ReIDEncoderHIP.forward
+        if self.training:
+            return enc.adapt(u8, self.momentum, output)
+        return enc.forward_running(u8, output)
+
+    def get_features(self, x, output_option=None):
+        output = self.output_option if output_option is None else output_option
+        if output not in ("plain", "norm", "neck"):
+            raise ValueError("output_option %r (plain / norm / neck)" % (output,))
+        enc = self._sync()
+        u8 = _to_u8_hwc_bgr(x, self._dev())
+        assert tuple(u8.shape[1:3]) == ReID_Encoder.PRETRAINED_SIZE
+        if self.precision != "x3":
+            return None, self._run(enc, u8, output)
+        updates = not self.use_domain_adaptation and self.training and self.momentum != 0.0
+        before = enc.running_stats() if updates else None         # what the exact extractor must start from should this batch leave the x3 range
+        feats = self._run(enc, u8, output)
+        torch.cuda.current_stream(self._dev()).synchronize()
+        if not enc.take_status():
+            return None, feats
+        if self._exact is None:
+            self._exact = ReIDEncoderHIP(_lib.Context(self._device_index), self._sd, precision="f32")
+        self.exact_reruns += 1
+        self._exact.load_running_stats(before if updates else enc.running_stats())
+        feats = self._run(self._exact, u8, output)
+        if updates:
+            enc.load_running_stats(self._exact.running_stats())
+        return None, feats
+
+    __call__ = get_features
+    forward = get_features

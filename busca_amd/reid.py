@@ -1,4 +1,4 @@
-"""Host handle of the ReID feature extractor kernels (busca_reid_* in include/busca_hip.h)."""
+"""Host handle of the ReID feature extractor kernels (busca_reid_* in include/busca_hip.h and include/busca_reid_bn.h)."""
 import weakref
 
 import numpy as np
@@ -8,6 +8,7 @@ from . import geometry, weights
 
 
 PRECISIONS = {"f32": 0, "f16": 1, "x3": 2}          # BUSCA_PREC_F32 / _F16 / _F16X3 (include/busca_hip.h)
+OUTPUTS = {"plain": 0, "norm": 1, "neck": 1}        # BUSCA_REID_OUT_* (include/busca_reid_bn.h); the encoder has no neck: `neck` returns fc7 like `norm` (resnet.py:329-334)
 
 
 def _ptr(t):
@@ -15,8 +16,9 @@ def _ptr(t):
 
 
 class ReIDEncoderHIP:
-    """ResNet-50 (max pool, red=4) with batch-statistics BatchNorm, fp16 MFMA convs.
-    `forward(crops_u8)`: u8 [n,384,128,3] BGR -> f32 [n,512] L2-normalised.  One call == one BN batch."""
+    """ResNet-50 (max pool, red=4), fp16 MFMA convs.
+    `forward(crops_u8)`: u8 [n,384,128,3] BGR -> f32 [n,512] L2-normalised, batch-statistics BatchNorm: one call == one BN batch.
+    `forward_running` / `adapt`: torch's eval-mode forward on running statistics and its train-mode update of them (include/busca_reid_bn.h)."""
     PRETRAINED_SIZE = (384, 128)
 
     def __init__(self, ctx, state_dict, prefix="", precision="f16"):
@@ -28,6 +30,8 @@ class ReIDEncoderHIP:
         self.ctx = ctx
         self.precision = precision
         self._blob = weights.reid_blob(state_dict, prefix)
+        self._running = None                # host copy of the running statistics the context should hold (None: none loaded); stale while `_running_dirty`
+        self._running_dirty = False         # an adapt() moved the device's statistics since `_running` was read
         if precision == "x3":
             # a HINT only (a loose static bound: 48 sigma, summed over a layer's bottlenecks): the kernels themselves report an operand that leaves the
             # split-fp16 range at run time (`take_status`), and BUSCA.settle re-runs such a batch on the exact-f32 extractor
@@ -39,13 +43,84 @@ class ReIDEncoderHIP:
     def _upload(self):
         ctx = self.ctx
         ctx.check(ctx.lib.busca_reid_load_weights_ex(ctx.h, self._blob.ctypes.data, self._blob.size, PRECISIONS[self.precision]))
+        if self._running is not None:       # the weight load dropped them
+            ctx.check(ctx.lib.busca_reid_load_running_stats(ctx.h, self._running.ctypes.data, self._running.size))
         ctx.reid_owner = weakref.ref(self)
 
     def _ensure_loaded(self):
-        """A busca_ctx holds ONE ReID weight set; restore this model's if another handle replaced it (see dt.py)."""
+        """A busca_ctx holds ONE ReID weight set and its running statistics; restore this model's if another handle replaced them (see dt.py).
+        The handle that is replaced saves statistics an adapt() has moved first (`_yield_context`)."""
         owner = getattr(self.ctx, "reid_owner", None)
-        if owner is None or owner() is not self:
+        other = owner() if owner is not None else None
+        if other is not self:
+            if other is not None:
+                other._yield_context()
             self._upload()
+
+    def _yield_context(self):
+        """Another handle is about to load its weights into this context: keep what adapt() did to the running statistics."""
+        if self._running_dirty:
+            self._running = self._read_running()
+            self._running_dirty = False
+
+    def _read_running(self):
+        out = np.empty(self.ctx.lib.busca_reid_running_floats(), np.float32)
+        s = torch.cuda.current_stream(torch.device("cuda", self.ctx.device)).cuda_stream
+        self.ctx.check(self.ctx.lib.busca_reid_get_running_stats(self.ctx.h, out.ctypes.data, out.size, s))
+        return out
+
+    # ---- running-statistics BatchNorm (include/busca_reid_bn.h) ----------------------------------------------------------
+    def load_running_stats(self, sd_or_blob, prefix=""):
+        """A state_dict with `running_mean` / `running_var` of every BatchNorm (weights.reid_running_blob) or the flat blob itself."""
+        blob = weights.reid_running_blob(sd_or_blob, prefix) if hasattr(sd_or_blob, "keys") else np.ascontiguousarray(sd_or_blob, dtype=np.float32).ravel()
+        self._ensure_loaded()
+        self.ctx.check(self.ctx.lib.busca_reid_load_running_stats(self.ctx.h, blob.ctypes.data, blob.size))
+        self._running, self._running_dirty = blob.copy(), False
+
+    def reset_running_stats(self):
+        """BatchNorm2d.reset_running_stats() on every BatchNorm: mean 0, variance 1."""
+        self._ensure_loaded()
+        self.ctx.check(self.ctx.lib.busca_reid_reset_running_stats(self.ctx.h))
+        self._running, self._running_dirty = weights.reid_running_reset(), False
+
+    def running_stats(self):
+        """The running statistics as the device holds them now (numpy [2 x 26 560], the layout of weights.reid_running_blob); synchronises the current stream."""
+        self._ensure_loaded()
+        self._running, self._running_dirty = self._read_running(), False
+        return self._running.copy()
+
+    def _crops(self, crops_u8):
+        dev = torch.device("cuda", self.ctx.device)
+        if not torch.is_tensor(crops_u8):
+            crops_u8 = torch.from_numpy(np.ascontiguousarray(crops_u8))
+        crops_u8 = crops_u8.to(dev).contiguous()
+        assert crops_u8.dtype == torch.uint8 and tuple(crops_u8.shape[1:]) == (384, 128, 3), crops_u8.shape
+        return dev, crops_u8
+
+    def forward_running(self, crops_u8, output="plain", stream=None, zero_norm=None):
+        """Eval-mode forward: BatchNorm on the running statistics, so crop i's features depend on crop i alone.  `output`: "plain" (L2-normalised, as
+        `forward`), "norm" (fc7 as it is) or "neck" (= "norm": the encoder has no neck)."""
+        self._ensure_loaded()
+        dev, crops_u8 = self._crops(crops_u8)
+        n = crops_u8.shape[0]
+        feats = torch.empty(n, 512, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        self.ctx.check(self.ctx.lib.busca_reid_forward_running(self.ctx.h, crops_u8.data_ptr(), n, _ptr(zero_norm), OUTPUTS[output], feats.data_ptr(), s))
+        return feats
+
+    def adapt(self, crops_u8, momentum, output="plain", stream=None, zero_norm=None):
+        """Train-mode forward: batch-statistics features (those of `forward`) and torch's update of the running statistics,
+        running = (1 - momentum) running + momentum batch with the unbiased batch variance, on the stream.  momentum 0 changes nothing and needs no
+        running statistics: a batch-statistics forward with an `output` choice."""
+        self._ensure_loaded()
+        dev, crops_u8 = self._crops(crops_u8)
+        n = crops_u8.shape[0]
+        feats = torch.empty(n, 512, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        self.ctx.check(self.ctx.lib.busca_reid_adapt(self.ctx.h, crops_u8.data_ptr(), n, _ptr(zero_norm), float(momentum), OUTPUTS[output], feats.data_ptr(), s))
+        if float(momentum) != 0.0 and n > 0:
+            self._running_dirty = True
+        return feats
 
     def take_status(self):
         """Call once the streams of this extractor's forwards are SYNCHRONISED.  True: a split-fp16 (x3) forward since the last call staged an activation beyond

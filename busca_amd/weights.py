@@ -75,12 +75,35 @@ def reid_conv_names():
 def reid_blob(state_dict, prefix=""):
     """ReID blob: per conv (forward order) weight[Cout,Cin,k,k], bn.weight, bn.bias; then red.weight, red.bias.
     `prefix` is 'reid_encoder.model.' for a full BUSCA checkpoint.  BN running statistics and the unused
-    classifier `fc` are not part of the blob (train-mode BN never reads them, network.py:553-556)."""
+    classifier `fc` are not part of the blob (train-mode BN never reads them, network.py:553-556); the statistics
+    have a blob of their own, `reid_running_blob`."""
     parts = []
     for conv, bn in reid_conv_names():
         parts += [_np(state_dict[prefix + conv + ".weight"]).ravel(), _np(state_dict[prefix + bn + ".weight"]).ravel(),
                   _np(state_dict[prefix + bn + ".bias"]).ravel()]
     parts += [_np(state_dict[prefix + "red.weight"]).ravel(), _np(state_dict[prefix + "red.bias"]).ravel()]
+    return np.concatenate(parts)
+
+
+def reid_running_blob(state_dict, prefix=""):
+    """BatchNorm running statistics of a ReID state_dict as busca_reid_load_running_stats takes them: per conv in the order of `reid_blob`
+    running_mean[Cout], then running_var[Cout] (2 x 26 560 floats).  A checkpoint without one of them raises KeyError naming the key."""
+    parts = []
+    for _, bn in reid_conv_names():
+        for stat in ("running_mean", "running_var"):
+            key = prefix + bn + "." + stat
+            if key not in state_dict:
+                raise KeyError("state_dict lacks %s" % key)
+            parts.append(_np(state_dict[key]).ravel())
+    return np.concatenate(parts)
+
+
+def reid_running_reset():
+    """The blob of BatchNorm2d.reset_running_stats(): mean 0, variance 1."""
+    from . import synth
+    parts = []
+    for spec in synth.reid_conv_specs():
+        parts += [np.zeros(spec[1], np.float32), np.ones(spec[1], np.float32)]
     return np.concatenate(parts)
 
 
