@@ -1,4 +1,4 @@
-"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h, include/busca_appearance.h, include/busca_ghost.h, include/busca_reid_bn.h).  No fallback: if the library is missing the
+"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h, include/busca_appearance.h, include/busca_ghost.h, include/busca_ghost_motion.h, include/busca_reid_bn.h).  No fallback: if the library is missing the
 import of any compute path raises - the product never computes on the CPU."""
 import ctypes as C
 import os
@@ -85,6 +85,13 @@ GHOST_MIN, GHOST_MEAN, GHOST_MAX, GHOST_MIDRANGE, GHOST_MEDIAN = 0, 1, 2, 3, 4  
 GHOST_MEDIAN_BUDGET_MAX = 256                                                        # BUSCA_GHOST_MEDIAN_BUDGET_MAX
 GHOST_PROXY_LAST, GHOST_PROXY_FIRST, GHOST_PROXY_MEAN, GHOST_PROXY_MEANNORM, GHOST_PROXY_MEDIAN = 0, 1, 2, 3, 4     # BUSCA_GHOST_PROXY_* modes
 
+# include/busca_ghost_motion.h
+GHOST_MOTION_SIGNATURES = {
+    "busca_ghost_motion_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "busca_ghost_motion_warp": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "busca_ghost_motion_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+}
+
 # include/busca_reid_bn.h
 REID_BN_SIGNATURES = {
     "busca_reid_running_floats": (_sz, []),
@@ -111,7 +118,7 @@ def load():
         # runtime (same device pointers, same streams).  Loading in the other order gives two runtimes.
         import torch  # noqa: F401
         lib = C.CDLL(os.environ.get("BUSCA_HIP_LIB", LIB_PATH))      # override: experiment builds of the same ABI
-        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + list(APPEARANCE_SIGNATURES.items()) + list(GHOST_SIGNATURES.items()) + list(REID_BN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + list(APPEARANCE_SIGNATURES.items()) + list(GHOST_SIGNATURES.items()) + list(GHOST_MOTION_SIGNATURES.items()) + list(REID_BN_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -15,7 +15,7 @@ OUT = os.path.join(HERE, "libbusca_hip.so")
 STAMP = OUT + ".flags"
 # (unit, compiled with -amdgpu-mfma-vgpr-form where that compiles).  busca_dt_aux: the instantiations that crash that pass (see the file).
 UNITS = [("busca_hip", True), ("busca_dt_f32", True), ("busca_dt_f16", True), ("busca_dt_x3", True), ("busca_dt_aux", False),
-         ("busca_dtl_f32", True), ("busca_dtl_f16", True), ("busca_dtl_x3", True), ("busca_reid", True), ("busca_assign", False), ("busca_appear", False), ("busca_ghost", False)]
+         ("busca_dtl_f32", True), ("busca_dtl_f16", True), ("busca_dtl_x3", True), ("busca_reid", True), ("busca_assign", False), ("busca_appear", False), ("busca_ghost", False), ("busca_ghost_motion", False)]
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 
 
@@ -88,6 +88,7 @@ def build(force=False, verbose=False):
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_assign.h"))
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_appearance.h"))
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ghost.h"))
+    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ghost_motion.h"))
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_reid_bn.h"))
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= _newest(all_deps) and (stamp_ok or not have_hipcc):
         return OUT

@@ -42,7 +42,7 @@ static void options_from_env(BuscaOptions& o) {
         if (const char* t = e.env ? getenv(e.env) : nullptr) o.*e.field = e.kind == OPT_PRESENT ? 1 : atoi(t);
 }
 
-extern "C" int busca_version(void) { return 2004; }      // 2004: running-statistics BatchNorm of the ReID extractor (include/busca_reid_bn.h); 2003: busca_ghost_* (include/busca_ghost.h); 2002: busca_appearance_cost (include/busca_appearance.h); 2001: busca_linear_assignment (include/busca_assign.h)
+extern "C" int busca_version(void) { return 2005; }      // 2005: busca_ghost_motion_* (include/busca_ghost_motion.h); 2004: running-statistics BatchNorm of the ReID extractor (include/busca_reid_bn.h); 2003: busca_ghost_* (include/busca_ghost.h); 2002: busca_appearance_cost (include/busca_appearance.h); 2001: busca_linear_assignment (include/busca_assign.h)
 
 static std::string g_create_err;   // busca_last_error(NULL) reports why busca_ctx_create failed
 

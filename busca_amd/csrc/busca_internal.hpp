@@ -7,6 +7,7 @@
 //   busca_assign.hip   the linear-assignment solver and its C-ABI (include/busca_assign.h)
 //   busca_appear.hip   the cosine gallery-cost kernel and its C-ABI (include/busca_appearance.h)
 //   busca_ghost.hip    GHOST's proxy distances, proxies, thresholds and mask / blend pass and their C-ABI (include/busca_ghost.h)
+//   busca_ghost_motion.hip   GHOST's linear motion model - position rings, velocity step, camera warp - and its C-ABI (include/busca_ghost_motion.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
