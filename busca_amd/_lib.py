@@ -1,4 +1,4 @@
-"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h, include/busca_appearance.h, include/busca_ghost.h, include/busca_ghost_motion.h, include/busca_reid_bn.h).  No fallback: if the library is missing the
+"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h, include/busca_appearance.h, include/busca_ghost.h, include/busca_ghost_motion.h, include/busca_reid_bn.h, include/busca_ecc.h).  No fallback: if the library is missing the
 import of any compute path raises - the product never computes on the CPU."""
 import ctypes as C
 import os
@@ -103,6 +103,16 @@ REID_BN_SIGNATURES = {
 }
 REID_OUT_PLAIN, REID_OUT_NORM = 0, 1                # BUSCA_REID_OUT_*
 
+# include/busca_ecc.h
+_i64 = C.c_int64
+ECC_SIGNATURES = {
+    "busca_ecc_gauss_taps": (C.c_int, [_i32, _vp]),
+    "busca_ecc_prepare": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "busca_ecc_align_planes": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, C.POINTER(C.c_double), C.POINTER(_i32), _vp]),
+}
+ECC_KSIZE_MAX = 31                                                  # BUSCA_ECC_KSIZE_MAX
+ECC_EUCLIDEAN, ECC_AFFINE, ECC_TRANSLATION = 0, 1, 2                # BUSCA_ECC_* motion codes
+
 _lib = None
 
 
@@ -118,7 +128,7 @@ def load():
         # runtime (same device pointers, same streams).  Loading in the other order gives two runtimes.
         import torch  # noqa: F401
         lib = C.CDLL(os.environ.get("BUSCA_HIP_LIB", LIB_PATH))      # override: experiment builds of the same ABI
-        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + list(APPEARANCE_SIGNATURES.items()) + list(GHOST_SIGNATURES.items()) + list(GHOST_MOTION_SIGNATURES.items()) + list(REID_BN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + list(APPEARANCE_SIGNATURES.items()) + list(GHOST_SIGNATURES.items()) + list(GHOST_MOTION_SIGNATURES.items()) + list(REID_BN_SIGNATURES.items()) + list(ECC_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

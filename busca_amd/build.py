@@ -90,6 +90,7 @@ def build(force=False, verbose=False):
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ghost.h"))
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ghost_motion.h"))
     all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_reid_bn.h"))
+    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ecc.h"))
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= _newest(all_deps) and (stamp_ok or not have_hipcc):
         return OUT
     if not have_hipcc:

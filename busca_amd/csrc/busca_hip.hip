@@ -1,6 +1,9 @@
 // libbusca_hip.so, core unit - C-ABI of include/busca_hip.h over the HIP kernels in this directory (the other units: busca_internal.hpp).
 // Written for gfx950 (MI355X) only.  hipcc --offload-arch=gfx950 (see busca_amd/build.py).
 #include "busca_internal.hpp"
+#pragma GCC visibility push(default)
+#include "../../include/busca_ecc.h"
+#pragma GCC visibility pop
 
 #define BUSCA_DT_BUCKET_KERNEL 1
 #include "dt_kernel.hip.inc"
@@ -8,6 +11,7 @@
 #include "track_kernel.hip.inc"
 #include "crop_kernel.hip.inc"
 #include "ecc_kernel.hip.inc"
+#include "ecc_f32_kernel.hip.inc"
 
 int ensure_lds(busca_ctx* c, const void* kern, size_t bytes) {
     if (c->lds_configured.count(kern)) return BUSCA_OK;
@@ -42,7 +46,7 @@ static void options_from_env(BuscaOptions& o) {
         if (const char* t = e.env ? getenv(e.env) : nullptr) o.*e.field = e.kind == OPT_PRESENT ? 1 : atoi(t);
 }
 
-extern "C" int busca_version(void) { return 2005; }      // 2005: busca_ghost_motion_* (include/busca_ghost_motion.h); 2004: running-statistics BatchNorm of the ReID extractor (include/busca_reid_bn.h); 2003: busca_ghost_* (include/busca_ghost.h); 2002: busca_appearance_cost (include/busca_appearance.h); 2001: busca_linear_assignment (include/busca_assign.h)
+extern "C" int busca_version(void) { return 2006; }      // 2006: busca_ecc_gauss_taps / _prepare / _align_planes (include/busca_ecc.h); 2005: busca_ghost_motion_* (include/busca_ghost_motion.h); 2004: running-statistics BatchNorm of the ReID extractor (include/busca_reid_bn.h); 2003: busca_ghost_* (include/busca_ghost.h); 2002: busca_appearance_cost (include/busca_appearance.h); 2001: busca_linear_assignment (include/busca_assign.h)
 
 static std::string g_create_err;   // busca_last_error(NULL) reports why busca_ctx_create failed
 

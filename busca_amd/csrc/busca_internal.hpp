@@ -96,7 +96,7 @@ struct busca_ctx {
     int* crop_fill = nullptr;      // per-crop pad value scratch (busca_crop_gather)
     int crop_fill_cap = 0;
     std::set<const void*> lds_configured;   // kernels whose dynamic-LDS limit was raised on THIS device
-    void* ecc_ws = nullptr; size_t ecc_ws_bytes = 0;    // busca_ecc_align scratch: 5 float images + partials
+    void* ecc_ws = nullptr; size_t ecc_ws_bytes = 0;    // scratch of busca_ecc_align / busca_ecc_prepare / busca_ecc_align_planes: 5 float images + partials
 };
 
 // Raise a kernel's dynamic LDS limit once per context (the attribute is per device, so a process driving several

@@ -213,35 +213,26 @@ static bool ecc_invert(const double* a, int n, float* out) {
     return true;
 }
 
-extern "C" int busca_ecc_align(busca_ctx* c, const uint8_t* prev, const uint8_t* cur, int32_t H, int32_t W, int32_t stride_prev,
-                               int32_t stride_cur, int32_t motion, int32_t max_iters, double eps, float* warp, double* cc, int32_t* iters_out,
-                               void* stream) {
-    if (!c) return BUSCA_EINVAL;
-    if (!prev || !cur || !warp || H < 8 || W < 8 || stride_prev < 3 * W || stride_cur < 3 * W || max_iters < 1 || (motion != 0 && motion != 1))
-        return fail(c, BUSCA_EINVAL, "busca_ecc_align: bad argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const size_t npix = (size_t)H * W, img = (npix * 4 + 255) & ~(size_t)255;
-    const int P = motion == 0 ? 3 : 6, NS = ECC_NS(P);
-    const size_t need = 5 * img + (size_t)(ECC_MAX_BLOCKS + 1) * ECC_NS(6) * 8;
+// The workspace of the ECC calls: 5 float images (template, input, gx, gy, one temporary) + the partial sums.  Growth waits for `s` (work
+// queued on it may still read the old block), frees and allocates.
+static int ecc_ws_reserve(busca_ctx* c, const char* who, size_t need, hipStream_t s) {
     if (c->ecc_ws_bytes < need) {
         if (c->ecc_ws) { HIP_TRY(c, hipStreamSynchronize(s)); HIP_TRY(c, hipFree(c->ecc_ws)); c->ecc_ws = nullptr; c->ecc_ws_bytes = 0; }
-        if (hipMalloc(&c->ecc_ws, need) != hipSuccess) return fail(c, BUSCA_ENOMEM, "busca_ecc_align: cannot allocate %zu bytes", need);
+        if (hipMalloc(&c->ecc_ws, need) != hipSuccess) return fail(c, BUSCA_ENOMEM, "%s: cannot allocate %zu bytes", who, need);
         c->ecc_ws_bytes = need;
     }
-    char* base = (char*)c->ecc_ws;
-    float *T = (float*)base, *I = (float*)(base + img), *gx = (float*)(base + 2 * img), *gy = (float*)(base + 3 * img), *tmp = (float*)(base + 4 * img);
-    double* partials = (double*)(base + 5 * img);
+    return BUSCA_OK;
+}
+static size_t ecc_img_bytes(int H, int W) { return ((size_t)H * W * 4 + 255) & ~(size_t)255; }
+static size_t ecc_ws_need(int H, int W) { return 5 * ecc_img_bytes(H, W) + (size_t)(ECC_MAX_BLOCKS + 1) * ECC_NS(6) * 8; }
+
+// The iterations of cv2.findTransformECC on a blurred template T, a blurred image I and its gradients: one ecc_iter_kernel<P> pass + the P x P
+// solve on the host per iteration (P = 2 translation, 3 Euclidean, 6 affine).  `who` names the entry point in the messages.
+static int ecc_iterate(busca_ctx* c, const char* who, const float* T, const float* I, const float* gx, const float* gy, int H, int W, int P, double* partials,
+                       int max_iters, double eps, float* warp, double* cc, int32_t* iters_out, hipStream_t s) {
+    const size_t npix = (size_t)H * W;
+    const int NS = ECC_NS(P);
     double* sums_d = partials + (size_t)ECC_MAX_BLOCKS * ECC_NS(6);
-    const dim3 g2((W + 255) / 256, H), b2(256);
-    hipLaunchKernelGGL(ecc_gray_kernel, g2, b2, 0, s, prev, H, W, stride_prev, tmp);
-    hipLaunchKernelGGL(ecc_blur_h_kernel, g2, b2, 0, s, (const float*)tmp, H, W, gx);
-    hipLaunchKernelGGL(ecc_blur_v_kernel, g2, b2, 0, s, (const float*)gx, H, W, T);
-    hipLaunchKernelGGL(ecc_gray_kernel, g2, b2, 0, s, cur, H, W, stride_cur, tmp);
-    hipLaunchKernelGGL(ecc_blur_h_kernel, g2, b2, 0, s, (const float*)tmp, H, W, gx);
-    hipLaunchKernelGGL(ecc_blur_v_kernel, g2, b2, 0, s, (const float*)gx, H, W, I);
-    hipLaunchKernelGGL(ecc_grad_kernel, g2, b2, 0, s, (const float*)I, H, W, gx, gy);
-    HIP_TRY(c, hipGetLastError());
     const int nblocks = (int)std::min<size_t>(ECC_MAX_BLOCKS, (npix + 1023) / 1024);
     float M[6];
     for (int i = 0; i < 6; ++i) M[i] = warp[i];
@@ -252,14 +243,15 @@ extern "C" int busca_ecc_align(busca_ctx* c, const uint8_t* prev, const uint8_t*
         a.T = T; a.I = I; a.gx = gx; a.gy = gy; a.H = H; a.W = W; a.partials = partials;
         for (int i = 0; i < 6; ++i) a.m[i] = (double)M[i];
         a.h0 = M[0]; a.h1 = M[3];
-        if (P == 3) hipLaunchKernelGGL((ecc_iter_kernel<3>), dim3(nblocks), dim3(256), 0, s, a);
+        if (P == 2) hipLaunchKernelGGL((ecc_iter_kernel<2>), dim3(nblocks), dim3(256), 0, s, a);
+        else if (P == 3) hipLaunchKernelGGL((ecc_iter_kernel<3>), dim3(nblocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((ecc_iter_kernel<6>), dim3(nblocks), dim3(256), 0, s, a);
         hipLaunchKernelGGL(ecc_reduce_kernel, dim3(1), dim3(64), 0, s, (const double*)partials, nblocks, NS, sums_d);
         double S[ECC_NS(6)];
         HIP_TRY(c, hipMemcpyAsync(S, sums_d, NS * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         const double n = S[0];
-        if (n < 1.0) return fail(c, BUSCA_EINVAL, "busca_ecc_align: the warped image does not overlap the template");
+        if (n < 1.0) return fail(c, BUSCA_EINVAL, "%s: the warped image does not overlap the template", who);
         const double mI = S[1] / n, mT = S[2] / n;
         const double img2 = S[3] - n * mI * mI, tmp2 = S[4] - n * mT * mT;      // n * variance
         const double corr = S[5] - n * mI * mT;
@@ -267,22 +259,24 @@ extern "C" int busca_ecc_align(busca_ctx* c, const uint8_t* prev, const uint8_t*
         int k = 6 + 3 * P;
         for (int i = 0; i < P; ++i)
             for (int j = i; j < P; ++j) { const float v = (float)S[k++]; hess[i * P + j] = v; hess[j * P + i] = v; }   // CV_32F hessian
-        if (!ecc_invert(hess, P, hinv)) return fail(c, BUSCA_EINVAL, "busca_ecc_align: singular Hessian");
+        if (!ecc_invert(hess, P, hinv)) return fail(c, BUSCA_EINVAL, "%s: singular Hessian", who);
         for (int i = 0; i < P; ++i) { ip[i] = (float)(S[6 + P + i] - mI * S[6 + i]); tp[i] = (float)(S[6 + 2 * P + i] - mT * S[6 + i]); }
         last_rho = rho;
         rho = corr / (sqrt(img2) * sqrt(tmp2));
-        if (rho != rho) return fail(c, BUSCA_EINVAL, "busca_ecc_align: NaN encountered");
+        if (rho != rho) return fail(c, BUSCA_EINVAL, "%s: NaN encountered", who);
         for (int i = 0; i < P; ++i) { float v = 0.f; for (int j = 0; j < P; ++j) v += hinv[i * P + j] * ip[j]; iph[i] = v; }
         double ipd = 0.0, tpd = 0.0;
         for (int i = 0; i < P; ++i) { ipd += (double)ip[i] * (double)iph[i]; tpd += (double)tp[i] * (double)iph[i]; }
         const double lam_n = img2 - ipd, lam_d = corr - tpd;
-        if (lam_d <= 0.0) return fail(c, BUSCA_EINVAL, "busca_ecc_align: the algorithm stopped before its convergence (correlation is going to be minimized)");
+        if (lam_d <= 0.0) return fail(c, BUSCA_EINVAL, "%s: the algorithm stopped before its convergence (correlation is going to be minimized)", who);
         const double lam = lam_n / lam_d;
         float ep[6], dp[6];
         for (int i = 0; i < P; ++i)       // J^T (lambda Tzm - Izm), by linearity from the unrounded sums
             ep[i] = (float)(lam * (S[6 + 2 * P + i] - mT * S[6 + i]) - (S[6 + P + i] - mI * S[6 + i]));
         for (int i = 0; i < P; ++i) { float v = 0.f; for (int j = 0; j < P; ++j) v += hinv[i * P + j] * ep[j]; dp[i] = v; }
-        if (P == 3) {
+        if (P == 2) {
+            M[2] += dp[0]; M[5] += dp[1];
+        } else if (P == 3) {
             const float th = asinf(M[3]) + dp[0];
             M[2] += dp[1]; M[5] += dp[2];
             M[0] = M[4] = cosf(th); M[3] = sinf(th); M[1] = -M[3];
@@ -294,4 +288,86 @@ extern "C" int busca_ecc_align(busca_ctx* c, const uint8_t* prev, const uint8_t*
     if (cc) *cc = rho;
     if (iters_out) *iters_out = it - 1;
     return BUSCA_OK;
+}
+
+extern "C" int busca_ecc_align(busca_ctx* c, const uint8_t* prev, const uint8_t* cur, int32_t H, int32_t W, int32_t stride_prev,
+                               int32_t stride_cur, int32_t motion, int32_t max_iters, double eps, float* warp, double* cc, int32_t* iters_out,
+                               void* stream) {
+    if (!c) return BUSCA_EINVAL;
+    if (!prev || !cur || !warp || H < 8 || W < 8 || stride_prev < 3 * W || stride_cur < 3 * W || max_iters < 1 || (motion != 0 && motion != 1))
+        return fail(c, BUSCA_EINVAL, "busca_ecc_align: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t img = ecc_img_bytes(H, W);
+    if (int rc = ecc_ws_reserve(c, "busca_ecc_align", ecc_ws_need(H, W), s)) return rc;
+    char* base = (char*)c->ecc_ws;
+    float *T = (float*)base, *I = (float*)(base + img), *gx = (float*)(base + 2 * img), *gy = (float*)(base + 3 * img), *tmp = (float*)(base + 4 * img);
+    double* partials = (double*)(base + 5 * img);
+    const dim3 g2((W + 255) / 256, H), b2(256);
+    hipLaunchKernelGGL(ecc_gray_kernel, g2, b2, 0, s, prev, H, W, stride_prev, tmp);
+    hipLaunchKernelGGL(ecc_blur_h_kernel, g2, b2, 0, s, (const float*)tmp, H, W, gx);
+    hipLaunchKernelGGL(ecc_blur_v_kernel, g2, b2, 0, s, (const float*)gx, H, W, T);
+    hipLaunchKernelGGL(ecc_gray_kernel, g2, b2, 0, s, cur, H, W, stride_cur, tmp);
+    hipLaunchKernelGGL(ecc_blur_h_kernel, g2, b2, 0, s, (const float*)tmp, H, W, gx);
+    hipLaunchKernelGGL(ecc_blur_v_kernel, g2, b2, 0, s, (const float*)gx, H, W, I);
+    hipLaunchKernelGGL(ecc_grad_kernel, g2, b2, 0, s, (const float*)I, H, W, gx, gy);
+    HIP_TRY(c, hipGetLastError());
+    return ecc_iterate(c, "busca_ecc_align", T, I, gx, gy, H, W, motion == 0 ? 3 : 6, partials, max_iters, eps, warp, cc, iters_out, s);
+}
+
+// ---- GHOST's camera-motion estimate (include/busca_ecc.h) --------------------------------------------------------------------
+static bool ecc_ksize_ok(int32_t k) { return k >= 1 && k <= ECC_KMAX && (k & 1); }
+
+extern "C" int busca_ecc_gauss_taps(int32_t ksize, float* taps) {
+    if (!taps || !ecc_ksize_ok(ksize)) return BUSCA_EINVAL;
+    static const float small[4][7] = {{1.f}, {0.25f, 0.5f, 0.25f}, {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f},
+                                      {0.03125f, 0.109375f, 0.21875f, 0.28125f, 0.21875f, 0.109375f, 0.03125f}};
+    if (ksize <= 7) {
+        for (int i = 0; i < ksize; ++i) taps[i] = small[ksize >> 1][i];
+        return BUSCA_OK;
+    }
+    const double sigma = 0.3 * ((ksize - 1) * 0.5 - 1) + 0.8, scale2 = -0.5 / (sigma * sigma);
+    double v[ECC_KMAX], sum = 0.0;
+    for (int i = 0; i < ksize; ++i) { const double x = i - (ksize - 1) * 0.5; v[i] = exp(scale2 * x * x); sum += v[i]; }
+    for (int i = 0; i < ksize; ++i) taps[i] = (float)(v[i] / sum);
+    return BUSCA_OK;
+}
+
+extern "C" int busca_ecc_prepare(busca_ctx* c, const float* img, int32_t channels, int32_t H, int32_t W, int64_t stride_c, int64_t stride_row,
+                                 int64_t stride_col, int32_t ksize, float* out, void* stream) {
+    if (!c) return BUSCA_EINVAL;
+    if (!ecc_ksize_ok(ksize)) return fail(c, BUSCA_EINVAL, "busca_ecc_prepare: ksize %d is not an odd size in 1 .. %d", ksize, ECC_KMAX);
+    const int lo = std::max(8, ksize / 2 + 1);
+    if (H < lo || W < lo) return fail(c, BUSCA_EINVAL, "busca_ecc_prepare: a %d x %d frame is below %d x %d (ksize %d)", H, W, lo, lo, ksize);
+    if (channels != 1 && channels != 3) return fail(c, BUSCA_EINVAL, "busca_ecc_prepare: %d channels (1 or 3)", channels);
+    if (!img || !out) return fail(c, BUSCA_EINVAL, "busca_ecc_prepare: null pointer");
+    if (stride_row < 0 || stride_col <= 0 || (channels == 3 && stride_c < 0)) return fail(c, BUSCA_EINVAL, "busca_ecc_prepare: bad stride");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ecc_ws_reserve(c, "busca_ecc_prepare", ecc_ws_need(H, W), s)) return rc;
+    float* tmp = (float*)((char*)c->ecc_ws + 4 * ecc_img_bytes(H, W));
+    EccTaps taps{};
+    busca_ecc_gauss_taps(ksize, taps.k);
+    const dim3 g2((W + ECC_TILE - 1) / ECC_TILE, H), b2(ECC_TILE);
+    hipLaunchKernelGGL(ecc_prep_h_kernel, g2, b2, 0, s, img, channels, H, W, (long)stride_c, (long)stride_row, (long)stride_col, taps, ksize, tmp);
+    hipLaunchKernelGGL(ecc_blur_vk_kernel, g2, b2, 0, s, (const float*)tmp, H, W, taps, ksize, out);
+    HIP_TRY(c, hipGetLastError());
+    return BUSCA_OK;
+}
+
+extern "C" int busca_ecc_align_planes(busca_ctx* c, const float* templ, const float* input, int32_t H, int32_t W, int32_t motion, int32_t max_iters,
+                                      double eps, float* warp, double* cc, int32_t* iters_out, void* stream) {
+    if (!c) return BUSCA_EINVAL;
+    if (!templ || !input || !warp || H < 8 || W < 8 || max_iters < 1 || motion < 0 || motion > 2)
+        return fail(c, BUSCA_EINVAL, "busca_ecc_align_planes: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t img = ecc_img_bytes(H, W);
+    if (int rc = ecc_ws_reserve(c, "busca_ecc_align_planes", ecc_ws_need(H, W), s)) return rc;
+    char* base = (char*)c->ecc_ws;
+    float *gx = (float*)(base + 2 * img), *gy = (float*)(base + 3 * img);
+    hipLaunchKernelGGL(ecc_grad_kernel, dim3((W + 255) / 256, H), dim3(256), 0, s, input, H, W, gx, gy);
+    HIP_TRY(c, hipGetLastError());
+    static const int P_OF[3] = {3, 6, 2};
+    return ecc_iterate(c, "busca_ecc_align_planes", templ, input, gx, gy, H, W, P_OF[motion], (double*)(base + 5 * img), max_iters, eps, warp, cc, iters_out, s);
 }

@@ -70,7 +70,7 @@ struct EccIterArgs {
     double* partials;        // [gridDim.x][NS]
 };
 
-// P = 3: Euclidean (theta, tx, ty); P = 6: affine.
+// P = 2: translation (tx, ty); P = 3: Euclidean (theta, tx, ty); P = 6: affine.
 template <int P>
 __global__ void __launch_bounds__(256) ecc_iter_kernel(const EccIterArgs g) {
 #pragma clang fp contract(off)
@@ -112,7 +112,9 @@ __global__ void __launch_bounds__(256) ecc_iter_kernel(const EccIterArgs g) {
         const float Tv = g.T[pix];
         float J[P];
         const float Xf = (float)x, Yf = (float)y;
-        if (P == 3) {
+        if constexpr (P == 2) {
+            J[0] = gxw; J[1] = gyw;
+        } else if constexpr (P == 3) {
             const float hatX = -(Xf * g.h1) - (Yf * g.h0), hatY = (Xf * g.h0) - (Yf * g.h1);
             J[0] = gxw * hatX + gyw * hatY; J[1] = gxw; J[2] = gyw;
         } else {

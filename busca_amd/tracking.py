@@ -996,6 +996,141 @@ class GhostMotion:
         return geometry.pairwise(self.ctx, pos, det_boxes, _lib.PAIR_IOU_COST)
 
 
+_GHOST_WARP_MODES = {"Translation": _lib.ECC_TRANSLATION, "Affine": _lib.ECC_AFFINE, "Euclidean": _lib.ECC_EUCLIDEAN}     # warp_mode_dct, base_tracker.py:60-65
+
+
+def ghost_ecc_check_config(motion_cfg):
+    """motion_config['warp_mode'] -> the motion code of busca_ecc_align_planes.  'Homography' is refused; an unknown name raises KeyError, as
+    `self.warp_mode_dct[...]` does."""
+    mode = motion_cfg["warp_mode"]
+    if mode == "Homography":
+        raise ValueError("GHOST warp_mode 'Homography' is refused: the reference always passes np.eye(2, 3) (base_tracker.py:613) and OpenCV asserts a "
+                         "3-row warp matrix for homographies, so this branch raises in the reference and there is nothing to reproduce")
+    return _GHOST_WARP_MODES[mode]
+
+
+def _ecc_frame(frame, dev):
+    """A float32 frame [3,H,W] or [H,W] on the device, strides kept (a host frame through pinned staging) -> (tensor, channels, H, W)."""
+    if not torch.is_tensor(frame):
+        frame = torch.from_numpy(np.asarray(frame))
+    if frame.dtype != torch.float32 or frame.dim() not in (2, 3) or (frame.dim() == 3 and frame.shape[0] != 3):
+        raise ValueError("an ECC frame is float32 [3,H,W] or [H,W], not %s %s" % (frame.dtype, tuple(frame.shape)))
+    if frame.device.type == "cpu":
+        frame = geometry.h2d_async(frame, dev)
+    elif frame.device != dev:
+        frame = frame.to(dev)
+    if any(s < 0 for s in frame.stride()) or frame.stride(-1) == 0:
+        frame = frame.contiguous()
+    return frame, (3 if frame.dim() == 3 else 1), int(frame.shape[-2]), int(frame.shape[-1])
+
+
+def _ecc_prepare(ctx, frame, channels, H, W, ksize, out):
+    """busca_ecc_prepare of a device frame into the [H,W] float32 plane `out`, on the current stream."""
+    dev = out.device
+    st = frame.stride()
+    ctx.check(ctx.lib.busca_ecc_prepare(ctx.h, frame.data_ptr(), channels, H, W, st[0] if channels == 3 else 0, st[-2], st[-1], int(ksize),
+                                        out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _ecc_align_planes(ctx, templ, inp, motion, iters, eps, warp):
+    """busca_ecc_align_planes on two [H,W] planes; `warp` (host float32 [2,3]) is updated in place -> (cc, iterations)."""
+    import ctypes as C
+    H, W = templ.shape
+    cc, its = C.c_double(0.0), C.c_int32(0)
+    ctx.check(ctx.lib.busca_ecc_align_planes(ctx.h, templ.data_ptr(), inp.data_ptr(), H, W, int(motion), int(iters), float(eps), warp.ctypes.data,
+                                             C.byref(cc), C.byref(its), torch.cuda.current_stream(templ.device).cuda_stream))
+    return cc.value, its.value
+
+
+def _ecc_motion_code(motion):
+    if isinstance(motion, str):
+        if motion == "MOTION_HOMOGRAPHY" or motion == "Homography":
+            raise ValueError("Invalid warp_mode: {}".format(motion))
+        return _GHOST_WARP_MODES[motion[7:].capitalize() if motion.startswith("MOTION_") else motion]
+    return int(motion)
+
+
+def find_transform_ecc_f32(template, input, warp_matrix=None, motion="Euclidean", gauss_size=15, number_of_iterations=100, termination_eps=1e-5,
+                           ctx=None):
+    """cv2.cvtColor(RGB2GRAY) + cv2.findTransformECC(template, input, warp_matrix, motion, criteria, None, gauss_size) on float32 frames, on the
+    GPU (busca_ecc_prepare x2 + busca_ecc_align_planes; OpenCV's arithmetic restated, parity unpinned: include/busca_ecc.h).  Frames: float32
+    [3,H,W] RGB or [H,W] grey, host arrays or cuda tensors of any strides.  motion: 'Translation' | 'Euclidean' | 'Affine' (GHOST's names) or
+    'MOTION_...' (OpenCV's).  Returns (cc, warp float32 [2,3]); raises BuscaError where OpenCV raises.  The stateless form, for callers with two
+    frames in hand: a tracker prepares every frame once with GhostCameraMotion."""
+    code = _ecc_motion_code(motion)
+    ctx = ctx or geometry.default_context()
+    dev = torch.device("cuda", ctx.device)
+    planes = []
+    for f in (template, input):
+        f, ch, H, W = _ecc_frame(f, dev)
+        planes.append(torch.empty(H, W, dtype=torch.float32, device=dev))
+        _ecc_prepare(ctx, f, ch, H, W, gauss_size, planes[-1])
+    if planes[0].shape != planes[1].shape:
+        raise ValueError("template %s and input %s differ in size" % (tuple(planes[0].shape), tuple(planes[1].shape)))
+    warp = np.eye(2, 3, dtype=np.float32) if warp_matrix is None else np.ascontiguousarray(warp_matrix, dtype=np.float32).reshape(2, 3).copy()
+    cc, its = _ecc_align_planes(ctx, planes[0], planes[1], code, number_of_iterations, termination_eps, warp)
+    find_transform_ecc_f32.last_iterations = its
+    return cc, warp
+
+
+class GhostCameraMotion:
+    """The estimate of GHOST's motion_compensation on the device (base_tracker.py:605-622, :633): every frame is prepared once - grey, 15-pixel
+    Gaussian (busca_ecc_prepare) - and its plane serves as the template of this frame's alignment and as the input of the next one's, so no
+    `last_image` is kept and no frame leaves the device.  Reads motion_cfg['warp_mode'], ['num_iter_mc'] and ['termination_eps_mc'].
+      estimate(whole_image)  float32 [3,H,W] cuda tensor of any strides (or a host tensor / array, uploaded through pinned staging) -> None on
+                             the first frame, then the float32 [2,3] warp of cv2.findTransformECC(current, previous, eye(2,3), ...)
+      norm, cc, iterations   of the last estimate: np.linalg.norm(warp[:, -1]) (the reference's warp_matrix_nomr; None on a first frame), the
+                             correlation coefficient, the iterations run
+      prepared               busca_ecc_prepare calls so far
+      reset()                a new sequence: the next frame is a first frame
+    Where OpenCV raises (no convergence, singular Hessian) estimate raises BuscaError and the stored plane stays the one of the last good frame,
+    as self.last_image does in the reference.  The two planes are allocated with the first frame and swapped from then on."""
+
+    def __init__(self, motion_cfg, gauss_size=15, ctx=None):
+        self.motion = ghost_ecc_check_config(motion_cfg)
+        self.iters, self.eps = int(motion_cfg["num_iter_mc"]), float(motion_cfg["termination_eps_mc"])
+        self.gauss_size = int(gauss_size)
+        if self.gauss_size < 1 or self.gauss_size > _lib.ECC_KSIZE_MAX or self.gauss_size % 2 == 0:
+            raise ValueError("gauss_size %d is not an odd size in 1 .. %d" % (self.gauss_size, _lib.ECC_KSIZE_MAX))
+        self.ctx = ctx or geometry.default_context()
+        self.dev = torch.device("cuda", self.ctx.device)
+        self._planes, self._cur = None, 0               # two [H,W] planes; _planes[_cur] is the stored (previous) frame's
+        self.prepared = 0
+        self.reset()
+
+    def reset(self):
+        self._have = False
+        self.norm = self.cc = self.iterations = None
+
+    def estimate(self, whole_image):
+        frame, ch, H, W = _ecc_frame(whole_image, self.dev)
+        if self._planes is None:
+            self._planes = [torch.empty(H, W, dtype=torch.float32, device=self.dev) for _ in range(2)]
+        elif tuple(self._planes[0].shape) != (H, W):
+            raise ValueError("GhostCameraMotion: a %d x %d frame in a sequence of %d x %d frames" % ((H, W) + tuple(self._planes[0].shape)))
+        new = self._planes[1 - self._cur]
+        _ecc_prepare(self.ctx, frame, ch, H, W, self.gauss_size, new)
+        self.prepared += 1
+        self.norm = None
+        warp = None
+        if self._have:
+            warp = np.eye(2, 3, dtype=np.float32)
+            self.cc, self.iterations = _ecc_align_planes(self.ctx, new, self._planes[self._cur], self.motion, self.iters, self.eps, warp)
+            self.norm = np.linalg.norm(warp[:, -1])
+        self._cur, self._have = 1 - self._cur, True
+        return warp
+
+
+def ghost_motion_compensation(camera, motion_state, whole_image, is_moving, enabled=True):
+    """BaseTracker.motion_compensation (base_tracker.py:600-633) on the device: the warp of this frame against the previous one
+    (camera: GhostCameraMotion) and, when the sequence has a moving camera (`is_moving`) and motion_config['motion_compensation'] (`enabled`),
+    every stored position of every track through it (motion_state: GhostMotion).  Returns the warp, None on the first frame."""
+    warp = camera.estimate(whole_image)
+    if warp is not None and is_moving and enabled:
+        motion_state.compensate(warp)
+    return warp
+
+
 def _ghost_get(state, name, default=None):
     return state.get(name, default) if isinstance(state, dict) else getattr(state, name, default)
 

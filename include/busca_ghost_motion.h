@@ -47,7 +47,8 @@ int busca_ghost_motion_append(busca_ctx* ctx, double* hist, int32_t* frames, int
  * float64, rounded ONCE to float32 and stored widened.  The reference rounds the corner to float32 first and runs a float32 torch.mm: this
  * result is within half a float32 ulp of the exact value, the reference's within its own float32 error of it.  After the call every
  * warped row holds float32 values, which is what `diff32` of busca_ghost_motion_step is about.
- *   warp   HOST f32 [6], row-major 2x3, read before the call returns (as busca_ecc_align's)
+ *   warp   HOST f32 [6], row-major 2x3, read before the call returns (as busca_ecc_align's); GHOST's own estimate is busca_ecc_prepare +
+ *          busca_ecc_align_planes (busca_ecc.h)
  * pos and vel are not touched: the reference does not warp Track.pos either, so an inactive track's extrapolated position stays in the
  * previous frame's coordinates until its next detection.  One thread per (slot, ring row, corner).  No listed slot: returns 0. */
 int busca_ghost_motion_warp(busca_ctx* ctx, double* hist, const int32_t* count, const int32_t* newest, int32_t S, int32_t H, const int32_t* slot, int32_t n,
