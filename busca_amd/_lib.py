@@ -1,4 +1,4 @@
-"""ctypes binding of libbusca_hip.so (include/busca_hip.h, include/busca_assign.h, include/busca_appearance.h, include/busca_ghost.h, include/busca_ghost_motion.h, include/busca_reid_bn.h, include/busca_ecc.h).  No fallback: if the library is missing the
+"""ctypes binding of libbusca_hip.so: one signature table per header under include/, listed in HEADERS.  No fallback: if the library is missing the
 import of any compute path raises - the product never computes on the CPU."""
 import ctypes as C
 import os
@@ -113,6 +113,11 @@ ECC_SIGNATURES = {
 ECC_KSIZE_MAX = 31                                                  # BUSCA_ECC_KSIZE_MAX
 ECC_EUCLIDEAN, ECC_AFFINE, ECC_TRANSLATION = 0, 1, 2                # BUSCA_ECC_* motion codes
 
+# header under include/ -> its signature table, in the order load() types them; a name lives in exactly one of them
+HEADERS = {"busca_hip.h": SIGNATURES, "busca_assign.h": ASSIGN_SIGNATURES, "busca_appearance.h": APPEARANCE_SIGNATURES, "busca_ghost.h": GHOST_SIGNATURES,
+           "busca_ghost_motion.h": GHOST_MOTION_SIGNATURES, "busca_reid_bn.h": REID_BN_SIGNATURES, "busca_ecc.h": ECC_SIGNATURES}
+__doc__ += "\nHeaders: " + ", ".join("include/" + h for h in HEADERS) + "."
+
 _lib = None
 
 
@@ -128,10 +133,11 @@ def load():
         # runtime (same device pointers, same streams).  Loading in the other order gives two runtimes.
         import torch  # noqa: F401
         lib = C.CDLL(os.environ.get("BUSCA_HIP_LIB", LIB_PATH))      # override: experiment builds of the same ABI
-        for name, (res, args) in list(SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + list(APPEARANCE_SIGNATURES.items()) + list(GHOST_SIGNATURES.items()) + list(GHOST_MOTION_SIGNATURES.items()) + list(REID_BN_SIGNATURES.items()) + list(ECC_SIGNATURES.items()):
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        for table in HEADERS.values():
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
         v = lib.busca_version()
         if v // 1000 != ABI_MAJOR:
             raise ImportError("libbusca_hip.so has ABI version %d, this binding needs major %d - rebuild (python -m busca_amd.build --force)" % (v, ABI_MAJOR))

@@ -27,7 +27,7 @@ CROP_BYTES = CROP_H * CROP_W * 3
 
 class Slot(np.lib.mixins.NDArrayOperatorsMixin):
     """One live crop of the pool AND the object a tracker stores (`crops[i]` of the lazy / device-only get_image_crops modes; alias
-    tracking.DeviceCrop): round 5 merged the two - one Python object per crop instead of a Slot, a DeviceCrop wrapper and a (frame, row) tuple.
+    crops.DeviceCrop): round 5 merged the two - one Python object per crop instead of a Slot, a DeviceCrop wrapper and a (frame, row) tuple.
     `ptr` is its device address (0 once spilled); `host` its host bytes (None until needed).  To duck-typing callers it is a uint8
     [384,128,3] array: any host read (`np.array(crop)`, arithmetic, `.astype`, indexing, pickling) returns the real pixels - from the
     frame's asynchronous host copy (lazy mode) or by copying the slot back on demand (device-only mode)."""
@@ -36,7 +36,7 @@ class Slot(np.lib.mixins.NDArrayOperatorsMixin):
 
     def __init__(self, pool, slab, index, ptr, host_src=None):
         self.pool, self.slab, self.index, self.ptr, self.host = pool, slab, index, ptr, None
-        self.host_src = host_src            # (frame host copy in flight, row): tracking.FrameHostCopy of get_image_crops' lazy mode
+        self.host_src = host_src            # (frame host copy in flight, row): crops.FrameHostCopy of get_image_crops' lazy mode
 
     @property
     def slot(self):

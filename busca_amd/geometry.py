@@ -3,6 +3,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._xfer import dev_of, h2d_async, stream_of, to_dev  # noqa: F401  (h2d_async: callers say geometry.h2d_async)
 
 _default_ctx = None
 
@@ -15,54 +16,47 @@ def default_context(device=0):
     return _default_ctx
 
 
-def _dev(ctx):
-    return torch.device("cuda", ctx.device)
-
-
-def _stream(ctx):
-    return torch.cuda.current_stream(_dev(ctx)).cuda_stream
+def ctx_dev(ctx=None):
+    """(ctx or the process-wide Context, its torch device): the prelude of every entry point that takes `ctx=None`.  Call it after the
+    early returns for empty inputs, which need no Context."""
+    ctx = ctx or default_context()
+    return ctx, dev_of(ctx)
 
 
 def _f64(x, ctx):
-    if not torch.is_tensor(x):
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64)))
-    return x.to(device=_dev(ctx), dtype=torch.float64).contiguous().view(-1, 4) if x.numel() else torch.zeros(0, 4, dtype=torch.float64, device=_dev(ctx))
+    x = to_dev(x, dev_of(ctx), torch.float64)
+    return x.view(-1, 4) if x.numel() else torch.zeros(0, 4, dtype=torch.float64, device=dev_of(ctx))
 
 
-def h2d_async(arr, dev, stream=None):
-    """Small host array -> device tensor without the host waiting for the stream: pinned staging (torch's caching host allocator keeps the block until the copy has
-    run) + an asynchronous copy.  A plain `.to(dev)` of a pageable array is a SYNCHRONOUS copy on the current stream: enqueued behind a ReID pass it parks the host
-    until the pass is done, and everything the host still has to enqueue (index gathers, the Decision-Transformer launch) then starts late.
-    `stream` (a raw HIP stream, or None for torch's current one): the stream of the kernel that reads the tensor - the copy is ordered on it."""
-    t = arr.contiguous() if torch.is_tensor(arr) else torch.from_numpy(np.ascontiguousarray(arr))
-    if t.device.type != "cpu":
-        return t.to(dev)
-    if stream is None:
-        return t.pin_memory().to(dev, non_blocking=True)
-    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-        return t.pin_memory().to(dev, non_blocking=True)
+def box_extents(bboxes):
+    """[n,4] x1y1x2y2 -> int32 (floor(x1), floor(y1), ceil(x2), ceil(y2)) on the caller's float64 values, as
+    busca/tracking.py:84-87 does with math.floor / math.ceil (a float32 copy of the box can land on the other side of
+    an integer).  Clamped to +-2^30 so absurd boxes cannot overflow the kernel's int arithmetic."""
+    b = np.nan_to_num(np.asarray(bboxes, dtype=np.float64).reshape(-1, 4), nan=0.0, posinf=2.0 ** 30, neginf=-2.0 ** 30)
+    r = np.empty(b.shape, np.float64)
+    r[:, :2] = np.floor(b[:, :2])
+    r[:, 2:] = np.ceil(b[:, 2:])
+    return np.clip(r, -2.0 ** 30, 2.0 ** 30).astype(np.int32)
 
 
 def pairwise(ctx, a, b, mode, scores_b=None):
     """[nA,4],[nB,4] float64 ltrb -> float64 [nA,nB] on the GPU (mode: _lib.PAIR_*)."""
     a, b = _f64(a, ctx), _f64(b, ctx)
-    out = torch.zeros(a.shape[0], b.shape[0], dtype=torch.float64, device=_dev(ctx))
+    out = torch.zeros(a.shape[0], b.shape[0], dtype=torch.float64, device=dev_of(ctx))
     sc = None
     if scores_b is not None:
-        sc = torch.as_tensor(np.asarray(scores_b, dtype=np.float64)).to(_dev(ctx)).contiguous()
+        sc = torch.as_tensor(np.asarray(scores_b, dtype=np.float64)).to(dev_of(ctx)).contiguous()
     ctx.check(ctx.lib.busca_pairwise(ctx.h, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], int(mode),
-                                     _lib.ptr(sc), out.data_ptr(), _stream(ctx)))
+                                     _lib.ptr(sc), out.data_ptr(), stream_of(ctx)))
     return out
 
 
 def topk_rows(ctx, dist, P):
     """float64 [B,N] -> int32 [B,P] indices of the P smallest per row (ties: lower index; -1 padding)."""
-    if not torch.is_tensor(dist):
-        dist = torch.from_numpy(np.ascontiguousarray(np.asarray(dist, dtype=np.float64)))
-    dist = dist.to(device=_dev(ctx), dtype=torch.float64).contiguous()
+    dist = to_dev(dist, dev_of(ctx), torch.float64)
     B, N = dist.shape
-    idx = torch.empty(B, P, dtype=torch.int32, device=_dev(ctx))
-    ctx.check(ctx.lib.busca_topk_rows(ctx.h, dist.data_ptr(), B, N, P, idx.data_ptr(), _stream(ctx)))
+    idx = torch.empty(B, P, dtype=torch.int32, device=dev_of(ctx))
+    ctx.check(ctx.lib.busca_topk_rows(ctx.h, dist.data_ptr(), B, N, P, idx.data_ptr(), stream_of(ctx)))
     return idx
 
 
@@ -86,8 +80,8 @@ def pairwise_host(ctx, a, b, mode, scores_b=None):
         tab[4 * (nA + nB):4 * (nA + nB) + ns] = np.asarray(scores_b, dtype=np.float64).reshape(-1)
     base, o = table.data_ptr(), 4 * (nA + nB) + ns
     ctx.check(ctx.lib.busca_pairwise(ctx.h, base, nA, base + 32 * nA, nB, int(mode), (base + 32 * (nA + nB)) if ns else None,
-                                     base + 8 * o, _stream(ctx)))
-    torch.cuda.current_stream(_dev(ctx)).synchronize()
+                                     base + 8 * o, stream_of(ctx)))
+    torch.cuda.current_stream(dev_of(ctx)).synchronize()
     return tab[o:].reshape(nA, nB).copy()
 
 
@@ -103,8 +97,8 @@ def topk_rows_host(ctx, dist, P):
     tab = table.numpy()
     tab[:B * N] = d.reshape(-1)
     base = table.data_ptr()
-    ctx.check(ctx.lib.busca_topk_rows(ctx.h, base, B, N, P, base + 8 * B * N, _stream(ctx)))
-    torch.cuda.current_stream(_dev(ctx)).synchronize()
+    ctx.check(ctx.lib.busca_topk_rows(ctx.h, base, B, N, P, base + 8 * B * N, stream_of(ctx)))
+    torch.cuda.current_stream(dev_of(ctx)).synchronize()
     return tab[B * N:].view(np.int32)[:B * P].reshape(B, P).copy()
 
 
@@ -120,8 +114,7 @@ def crop_gather(ctx, frame, boxes, want_u8=True, want_f16=False, dst_ptrs=None):
     """frame: u8 [H,W,3] BGR (numpy or cuda tensor); boxes [n,4] x1y1x2y2 (float: rounded to extents in float64 on the
     host; int32: already extents) -> (u8 [n,384,128,3] | None, fp16 [n,384,128,4] RGB0 normalised | None) on the GPU.
     `dst_ptrs` (uint64 [n]): write crop i to that device address instead (crop-pool slots)."""
-    from .tracking import box_extents
-    dev = _dev(ctx)
+    dev = dev_of(ctx)
     if torch.is_tensor(boxes):
         boxes = boxes.detach().cpu().numpy()
     boxes = np.asarray(boxes)
@@ -144,15 +137,14 @@ def crop_gather(ctx, frame, boxes, want_u8=True, want_f16=False, dst_ptrs=None):
             tab[2 * n:] = np.ascontiguousarray(dst_ptrs, dtype=np.uint64).view(np.int64)
         base = table.data_ptr()
         ctx.check(ctx.lib.busca_crop_gather_ex(ctx.h, frame.data_ptr(), H, W, frame.stride(0), base, n,
-                                               (base + 16 * n) if dst_ptrs is not None else None, _lib.ptr(u8), _lib.ptr(f16), _stream(ctx)))
+                                               (base + 16 * n) if dst_ptrs is not None else None, _lib.ptr(u8), _lib.ptr(f16), stream_of(ctx)))
         _keep_until_done(ctx, table, dev)
     return u8, f16
 
 
 def crop_gather_sized(ctx, frame, boxes, out_w, out_h):
     """Crops of an arbitrary output size (busca_crop_gather_sized): u8 [n, out_h, out_w, 3] on the GPU."""
-    from .tracking import box_extents
-    dev = _dev(ctx)
+    dev = dev_of(ctx)
     boxes = np.asarray(boxes.detach().cpu().numpy() if torch.is_tensor(boxes) else boxes)
     rects = boxes.reshape(-1, 4) if boxes.dtype == np.int32 else box_extents(boxes)
     frame, rects = _frame_for_rects(ctx, frame, rects, dev)
@@ -163,7 +155,7 @@ def crop_gather_sized(ctx, frame, boxes, out_w, out_h):
         table = torch.empty(n * 2, dtype=torch.int64, pin_memory=True)
         table.numpy()[:] = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1).view(np.int64)
         H, W = frame.shape[:2]
-        ctx.check(ctx.lib.busca_crop_gather_sized(ctx.h, frame.data_ptr(), H, W, frame.stride(0), table.data_ptr(), n, int(out_h), int(out_w), out.data_ptr(), _stream(ctx)))
+        ctx.check(ctx.lib.busca_crop_gather_sized(ctx.h, frame.data_ptr(), H, W, frame.stride(0), table.data_ptr(), n, int(out_h), int(out_w), out.data_ptr(), stream_of(ctx)))
         _keep_until_done(ctx, table, dev)
     return out
 
@@ -190,7 +182,7 @@ def begin_frame(ctx, frame):
     (identity; the scope holds a reference, so the id cannot be recycled) reuses the upload, and the caller promises not to edit the array inside the
     scope.  Without a scope every call uploads the array it is given - what busca/network.py:492-507 does with the live array - so no result ever
     depends on a guess about whether two host buffers hold the same pixels (rounds 2-4 guessed with a sparse pixel fingerprint: removed)."""
-    dev = _dev(ctx)
+    dev = dev_of(ctx)
     if torch.is_tensor(frame):
         t = frame.to(dev).contiguous()                    # (a CUDA tensor is used where it is; a CPU tensor is uploaded once)
     else:
@@ -269,12 +261,12 @@ def _frame_for_rects(ctx, frame, rects, dev):
 
 def gather_crops(ctx, src_ptrs):
     """uint64 [n] device addresses of 147 456-byte crops (0 = all-zero crop) -> cuda u8 [n,384,128,3] (busca_gather_crops)."""
-    dev = _dev(ctx)
+    dev = dev_of(ctx)
     n = len(src_ptrs)
     out = torch.empty(n, 384, 128, 3, dtype=torch.uint8, device=dev)
     if n:
         stage = torch.empty(n, dtype=torch.int64, pin_memory=True)                # pinned staging: the upload is asynchronous
         stage.numpy()[:] = np.ascontiguousarray(src_ptrs, dtype=np.uint64).view(np.int64)
         src = stage.to(dev, non_blocking=True)
-        ctx.check(ctx.lib.busca_gather_crops(ctx.h, src.data_ptr(), n, out.data_ptr(), _stream(ctx)))
+        ctx.check(ctx.lib.busca_gather_crops(ctx.h, src.data_ptr(), n, out.data_ptr(), stream_of(ctx)))
     return out

@@ -1,0 +1,261 @@
+"""GHOST's association on the device: proxy distances, per-track proxies, data-driven thresholds, the entrywise cost rules and the whole round.
+Fronts include/busca_ghost.h (and busca_linear_assignment for the solve); restates adapters/GHOST/src/tracker.py:272-480,
+tracking_utils.py:63-126 (get_proxy) and base_tracker.py:101-106,495-531,713-731."""
+import numpy as np
+import torch
+
+from . import _lib, geometry
+from ._xfer import stream_of, to_dev
+from .appearance import _check_width, gallery_operands
+from .assignment import _assign_dev
+from .ghost_motion import ghost_motion_check_config
+
+_GHOST_REDUCE = {"min": _lib.GHOST_MIN, "mean": _lib.GHOST_MEAN, "max": _lib.GHOST_MAX, "midrange": _lib.GHOST_MIDRANGE, "median": _lib.GHOST_MEDIAN,
+                 1: _lib.GHOST_MIN, 2: _lib.GHOST_MEAN, 3: _lib.GHOST_MAX, 4: _lib.GHOST_MIDRANGE, 5: _lib.GHOST_MEDIAN}      # tracker_cfg['avg_inact']['num']
+_GHOST_PROXY = {"last": _lib.GHOST_PROXY_LAST, "first": _lib.GHOST_PROXY_FIRST, "mean": _lib.GHOST_PROXY_MEAN, "meannorm": _lib.GHOST_PROXY_MEANNORM,
+                "median": _lib.GHOST_PROXY_MEDIAN}
+GHOST_LIMIT = 8192.0                    # the solver's limit in ghost_round: costs are <= 2 and n, m <= 2048, so one more match always beats any cost
+
+
+def ghost_distance(track_feats, det_feats, reduce="mean", slot=None, count=None, out=None, ctx=None):
+    """busca_ghost_distance: GHOST's proxy_dist (adapters/GHOST/src/tracker.py:278-296) for every track at once - the cosine distance between every
+    stored sample of a track and every detection, reduced per track.  `reduce`: 'min', 'mean', 'max', 'midrange' ((max + min) / 2) or 'median'
+    (np.median), or the reference's tracker_cfg['avg_inact']['num'] 1 .. 5.  Operands as appearance_cost; 'median' takes a budget of at most 256.
+    -> device float64 tensor [n,m], tracks x detections: GHOST's [detections, tracks] matrix is its `.T`.  `out`: a contiguous device [n,m] float64
+    tensor (or row block of one) to write into."""
+    if isinstance(reduce, str):
+        reduce = reduce.lower()
+    if reduce not in _GHOST_REDUCE:
+        raise ValueError("reduce must be 'min', 'mean', 'max', 'midrange', 'median' or GHOST's num 1 .. 5, not %r" % (reduce,))
+    ctx, dev = geometry.ctx_dev(ctx)
+    g, slot, count, n = gallery_operands(track_feats, slot, count, dev, "ghost_distance")
+    d = to_dev(det_feats, dev, torch.float32)
+    if d.dim() != 2:
+        raise ValueError("ghost_distance takes [m,E] detection features")
+    _check_width(g, d)
+    budget, E, m = g.shape[1], g.shape[2], d.shape[0]
+    if out is None:
+        out = torch.empty(n, m, dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (n, m) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float64 [%d,%d] device tensor" % (n, m))
+    ctx.check(ctx.lib.busca_ghost_distance(ctx.h, g.data_ptr(), _lib.ptr(slot), _lib.ptr(count), n, budget, d.data_ptr(), m, E, _GHOST_REDUCE[reduce],
+                                           out.data_ptr(), stream_of(dev)))
+    return out
+
+
+def ghost_proxies(gallery, mode="mean", window=0, slot=None, count=None, newest=None, ctx=None):
+    """busca_ghost_proxies: get_proxy (adapters/GHOST/src/tracking_utils.py:63-126) - one vector per track from its stored samples.
+      gallery  [S,budget,E] float32, a ring of `budget` rows per slot; slot / count as appearance_cost
+      newest   [S] ints or None: the ring row of every slot's newest sample (None: count - 1)
+      mode     'last', 'first' (the oldest stored sample), 'mean', 'meannorm', 'median' (torch.median: the lower one)
+      window   the newest `window` samples take part (tracker_cfg['avg_*']['num']); 0 or 'all', or more than a track has: all of them
+    torch.mode and the stateful 'mv_avg' are not built (mv_avg is `mv_avg * a + last * (1 - a)` on the caller's own tensor).
+    -> device float32 tensor [n,E]; a track without samples gets a row of NaN."""
+    if mode in ("mode", "mv_avg"):
+        raise NotImplementedError("ghost_proxies: the %r proxy is not built on the device (torch.mode has no kernel here; mv_avg is a stateful "
+                                  "moving average - keep it a tensor op of the caller's)" % (mode,))
+    if mode not in _GHOST_PROXY:
+        raise ValueError("mode must be one of %s, not %r" % (sorted(_GHOST_PROXY), mode))
+    window = 0 if window in (None, "all") else int(window)
+    ctx, dev = geometry.ctx_dev(ctx)
+    g, slot, count, n = gallery_operands(gallery, slot, count, dev, "ghost_proxies")
+    S, budget, E = g.shape
+    if newest is not None and len(newest) != S:
+        raise ValueError("newest has %d entries for %d slots" % (len(newest), S))
+    newest = to_dev(newest, dev, torch.int32, flat=True)
+    out = torch.empty(n, E, dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.busca_ghost_proxies(ctx.h, g.data_ptr(), _lib.ptr(slot), _lib.ptr(count), _lib.ptr(newest), n, budget, E, _GHOST_PROXY[mode], window,
+                                          out.data_ptr(), stream_of(dev)))
+    return out
+
+
+def ghost_thresholds(cost, num_active, k_act, k_inact, out=None, ctx=None):
+    """busca_ghost_thresholds: update_thresholds (adapters/GHOST/src/base_tracker.py:495-531) on a tracks x detections device matrix whose first
+    `num_active` rows are the active tracks: (mean - k_act * std of those rows, mean - k_inact * std of the others), np.std's population std; the
+    reference's k are (0, 2) with 'every' and (0.5, 1) with 'tbd'.  -> device float64 tensor [2], never synchronised: hand it to ghost_cost as it is.
+    A group without rows keeps its entry of `out` (a new tensor starts at +inf, a threshold nothing exceeds)."""
+    ctx, dev = geometry.ctx_dev(ctx)
+    cost = to_dev(cost, dev, torch.float64)
+    n, m = cost.shape
+    if out is None:
+        out = torch.full((2,), float("inf"), dtype=torch.float64, device=dev)
+    ctx.check(ctx.lib.busca_ghost_thresholds(ctx.h, cost.data_ptr(), n, m, int(num_active), float(k_act), float(k_inact), out.data_ptr(), stream_of(dev)))
+    return out
+
+
+def ghost_cost(app, motion=None, alpha=0.0, track_labels=None, det_labels=None, num_active=None, thr=None, ctx=None):
+    """busca_ghost_combine: the entrywise rest of GHOST's cost matrix on a tracks x detections matrix, in the reference's order - entries whose
+    track and detection labels differ become NaN (nan_over_classes, tracker.py:272-275 / :299-302), then (1 - alpha) * app + alpha * motion
+    (combine_motion_appearance with combi 'sum_<alpha>', base_tracker.py:713-731), then entries that are not <= thr[0] (the first `num_active` rows)
+    / thr[1] (the others) become NaN (nan_first, tracker.py:392-396).  Every part is optional.  `thr`: two numbers or a device float64 [2] tensor
+    (ghost_thresholds).  -> a new device float64 tensor [n,m]."""
+    ctx, dev = geometry.ctx_dev(ctx)
+    app = to_dev(app, dev, torch.float64)
+    n, m = app.shape
+    if motion is not None:
+        motion = to_dev(motion, dev, torch.float64)
+        if tuple(motion.shape) != (n, m):
+            raise ValueError("the motion cost is %s, the appearance cost %s: both are tracks x detections" % (tuple(motion.shape), (n, m)))
+    if (track_labels is None) != (det_labels is None):
+        raise ValueError("track_labels and det_labels go together")
+    tl, dl = to_dev(track_labels, dev, torch.int32, flat=True), to_dev(det_labels, dev, torch.int32, flat=True)
+    if tl is not None and (tl.numel() != n or dl.numel() != m):
+        raise ValueError("%d track labels and %d detection labels for a %d x %d matrix" % (tl.numel(), dl.numel(), n, m))
+    if thr is not None and not torch.is_tensor(thr):
+        thr = np.asarray(thr, dtype=np.float64).reshape(2)
+    thr = to_dev(thr, dev, torch.float64)
+    out = torch.empty(n, m, dtype=torch.float64, device=dev)
+    ctx.check(ctx.lib.busca_ghost_combine(ctx.h, app.data_ptr(), _lib.ptr(motion), n, m, float(alpha), _lib.ptr(tl), _lib.ptr(dl),
+                                          n if num_active is None else int(num_active), _lib.ptr(thr), out.data_ptr(), stream_of(dev)))
+    return out
+
+
+def ghost_check_config(cfg):
+    """Refuse the tracker_cfg branches that do not work in the reference either, and the ones that are not built; returns cfg."""
+    if cfg.get("use_bism", False):
+        raise ValueError("GHOST use_bism is refused: the reference crashes in this branch (bisoftmax already returns a numpy array and dist() calls "
+                         ".numpy() on it, base_tracker.py:105-106), so there is nothing to reproduce")
+    if cfg.get("distance", "cosine") != "cosine":
+        raise ValueError("GHOST distance %r is refused: only 'cosine' works in the reference (the other branch applies F.pairwise_distance to the "
+                         "broadcast [m, E, g] tensor, takes the norm over the gallery axis and returns [m, E], base_tracker.py:101)" % (cfg["distance"],))
+    return cfg
+
+
+def _ghost_get(state, name, default=None):
+    return state.get(name, default) if isinstance(state, dict) else getattr(state, name, default)
+
+
+def _ghost_proxy_rows(ctx, g, count, newest, slot, entry, what):
+    """get_proxy's choice for one group of tracks (tracker_cfg['avg_act'] / ['avg_inact']) -> device [k,E] float32."""
+    proxy, num = entry.get("proxy", "last"), entry.get("num", "all")
+    if not entry.get("do", False) or proxy == "last":            # without 'do', track.feats: the newest sample
+        mode, window = "last", 0
+    elif num == "first":
+        mode, window = "first", 0
+    elif proxy in ("mv_avg", "mode") or proxy not in _GHOST_PROXY:
+        raise NotImplementedError("ghost_round: %s proxy %r is not built on the device" % (what, proxy))
+    else:
+        mode, window = proxy, (0 if num == "all" else int(num))
+    return ghost_proxies(g, mode, window, slot=slot, count=count, newest=newest, ctx=ctx)
+
+
+def ghost_round(state, det_feats, labels=None, motion=None, cfg=None, sep=None, thresholds=None, ctx=None, det_boxes=None):
+    """GHOST's association round without leaving the device: get_hungarian_each_sample / get_hungarian_with_proxy + solve_hungarian
+    (adapters/GHOST/src/tracker.py:306-480) from the tracks' sample galleries and the detections' features in HBM to the matches on the host.
+      state       the tracks: a dict or object with `gallery` [S,budget,E] float32 (host array or device tensor), `count` [S] and `newest` [S] (or None,
+                  as ghost_proxies), `slot` [n] or None - the gallery slot of track i, ACTIVE TRACKS FIRST - and `num_active`
+      det_feats   [m,E] float32, host array or device tensor
+      labels      (track_labels [n], det_labels [m]) or None; as in the reference only the each_sample route masks classes
+      motion      [n,m] tracks x detections motion cost (host array or device tensor); needed when motion_config['apply_motion_model'],
+                  unless `state` carries `motion_state`, a GhostMotion whose slots are the gallery's, and `det_boxes` [m,4] tlbr is given: the round
+                  then runs the motion model itself (GhostMotion.cost with motion_config['last_n_frames']; it advances the positions, so once
+                  per frame, as the reference calls motion() in its round)
+      cfg         the reference's tracker_cfg: 'avg_act' / 'avg_inact' {'do', 'num', 'proxy'}, 'act_reid_thresh' / 'inact_reid_thresh' (numbers,
+                  'every' or 'tbd'), 'nan_first', 'assign_separately', 'motion_config' {'apply_motion_model', 'combi': 'sum_<alpha>'},
+                  'distance', 'use_bism'.  avg_inact['proxy'] == 'each_sample' selects the per-sample route, whose reduction is avg_inact['num'] 1 .. 5
+      sep         overrides cfg['assign_separately']: solve the active tracks only, as solve_hungarian does
+      thresholds  a device float64 [2] tensor to hold (act, inact): fixed thresholds are written into it, data-driven ones computed into it on
+                  the device - a 'tbd' caller reads it back once and passes numbers from then on
+    -> (dist, row, col): `dist` the device cost matrix in GHOST's [detections, tracks] orientation (a transposed view; with `sep` the list
+    [dist_act, dist_inact] the reference returns, dist_inact None without active tracks), `row` / `col` the matched detection / track indices as
+    host int arrays, sorted by detection.  One device->host copy of n + m + 1 ints; the post-filters assign_act_inact_same_time / assign_separatly
+    stay host code reading `row`, `col` and `dist`.
+
+    The solve is busca_linear_assignment with limit 8192: every cost is <= 2 and there are at most 2048 rows, so a matching with one more pair
+    always wins and among those the cheapest does - a maximum-cardinality minimum-cost matching over the non-NaN entries (NaN is never
+    admissible).  The reference calls lapsolver.solve_dense, whose behaviour on a matrix with infeasible rows is third-party and unpinned here: where
+    every detection can be matched the two agree; elsewhere this is the documented rule."""
+    cfg = ghost_check_config(dict(cfg or {}))
+    ctx, dev = geometry.ctx_dev(ctx)
+    g, slot, count, n = gallery_operands(_ghost_get(state, "gallery"), _ghost_get(state, "slot"), _ghost_get(state, "count"), dev, "ghost_round")
+    newest = to_dev(_ghost_get(state, "newest"), dev, torch.int32, flat=True)
+    na = _ghost_get(state, "num_active")
+    na = n if na is None else int(na)
+    if not 0 <= na <= n:
+        raise ValueError("num_active %d outside 0 .. %d" % (na, n))
+    d = to_dev(det_feats, dev, torch.float32)
+    m = d.shape[0]
+    sep = bool(cfg.get("assign_separately", False)) if sep is None else bool(sep)
+    empty = np.empty(0, dtype=np.int64)
+    if n == 0 or m == 0:
+        return torch.empty(m, n, dtype=torch.float64, device=dev), empty, empty
+    if slot is None:
+        slot = torch.arange(n, dtype=torch.int32, device=dev)
+    act, inact = cfg.get("avg_act", {}), cfg.get("avg_inact", {})
+    each = inact.get("proxy") == "each_sample"
+    app = torch.empty(n, m, dtype=torch.float64, device=dev)
+    def kind(entry):                                              # what a group of tracks runs: its rows depend on nothing else
+        if each:
+            return ("samples", inact.get("num", 2)) if entry.get("do", False) else ("last",)
+        return ("proxy", entry.get("proxy", "last"), entry.get("num", "all")) if entry.get("do", False) else ("last",)
+    groups = ((0, n, inact, "avg_inact"),) if kind(act) == kind(inact) else ((0, na, act, "avg_act"), (na, n, inact, "avg_inact"))      # one launch where both groups run the same
+    for lo, hi, entry, what in groups:
+        if hi == lo:
+            continue
+        if each and entry.get("do", False):                       # proxy_dist over the track's samples; both groups reduce with avg_inact['num']
+            ghost_distance(g, d, inact.get("num", 2), slot=slot[lo:hi], count=count, out=app[lo:hi], ctx=ctx)
+        else:                                                     # one vector per track (last_frame, or get_proxy), then the plain cosine distance
+            entry = {"do": False} if each else entry
+            ghost_distance(_ghost_proxy_rows(ctx, g, count, newest, slot[lo:hi], entry, what), d, "min", out=app[lo:hi], ctx=ctx)
+    tl = dl = None
+    if each and labels is not None and cfg.get("nan_over_classes", True):
+        tl, dl = labels
+    at, it = cfg.get("act_reid_thresh"), cfg.get("inact_reid_thresh")
+    every, tbd = at == "every", at == "tbd"
+    for name, v in (("act_reid_thresh", at), ("inact_reid_thresh", it)):
+        if isinstance(v, str) and v not in ("every", "tbd"):
+            raise ValueError("%s must be a number, 'every' or 'tbd', not %r" % (name, v))
+    data_act, data_inact = every or tbd, every or it == "tbd"
+    if it == "tbd" and not (every or tbd):
+        raise ValueError("inact_reid_thresh 'tbd' needs act_reid_thresh 'tbd' or 'every': the reference leaves it a string otherwise (base_tracker.py:515-531)")
+    mcfg = cfg.get("motion_config", {})
+    blend = bool(mcfg.get("apply_motion_model", False))
+    alpha = 0.0
+    if blend:
+        combi = str(mcfg.get("combi", ""))
+        if "sum" not in combi:
+            raise NotImplementedError("ghost_round: motion_config combi %r is not built; only 'sum_<alpha>'" % (combi,))
+        alpha = float(combi.split("_")[-1])
+        mstate = _ghost_get(state, "motion_state")
+        if motion is None and mstate is not None and det_boxes is not None:
+            ghost_motion_check_config(mcfg, cfg.get("kalman", False))
+            mslot = _ghost_get(state, "slot")
+            motion = mstate.cost(slot if mslot is None or torch.is_tensor(mslot) else mslot, na, det_boxes, mcfg.get("last_n_frames", 100000000))
+        if motion is None:
+            raise ValueError("motion_config applies a motion model: pass the [n,m] motion cost")
+    nan_first = bool(cfg.get("nan_first", False))
+    thr = None
+    if nan_first or data_act or data_inact:
+        fixed = [float("inf") if isinstance(v, str) or v is None else float(v) for v in (at, it)]
+        host_thr = torch.from_numpy(np.asarray(fixed, dtype=np.float64))
+        if thresholds is None:
+            thr = host_thr.to(dev)
+        else:
+            thr = thresholds
+            thr.copy_(host_thr)
+    if data_act or data_inact:
+        if tl is not None:                                        # solve_hungarian sees the class-masked matrix
+            app = ghost_cost(app, track_labels=tl, det_labels=dl, ctx=ctx)
+            tl = dl = None
+        k_act, k_inact = (0.0, 2.0) if every else (0.5, 1.0)
+        if data_act and data_inact:
+            ghost_thresholds(app, na, k_act, k_inact, out=thr, ctx=ctx)
+        elif na > 0:                                              # the active threshold only: over the active rows alone
+            ghost_thresholds(app[:na], na, k_act, k_inact, out=thr, ctx=ctx)
+    if tl is not None or blend or nan_first:
+        cost = ghost_cost(app, motion if blend else None, alpha, tl, dl, na, thr if nan_first else None, ctx=ctx)
+    else:
+        cost = app
+    rows = na if sep else n
+    if rows == 0:
+        row = col = empty
+    else:
+        sol = _assign_dev(ctx, cost, 1, rows, m, GHOST_LIMIT).cpu().numpy()[0]      # the leading `rows` rows of the contiguous matrix are a [rows,m] problem
+        if sol[rows + m] != 0:
+            raise _lib.BuscaError("ghost_round: the solver ran out of its loop bounds (status %d) - is a cost -inf?" % int(sol[rows + m]))
+        c2r = sol[rows:rows + m].astype(np.int64)
+        row = np.nonzero(c2r >= 0)[0]
+        col = c2r[row]
+    if sep:
+        return [cost[:na].T, cost[na:].T if na > 0 else None], row, col
+    return cost.T, row, col

@@ -12,7 +12,7 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 import torch
 
-from . import _lib, geometry, synth, tracking, weights
+from . import _lib, crops, geometry, synth, tracking, weights
 from .dt import DecisionTransformerHIP, DTOutput
 from .reid import ReIDEncoderHIP
 
@@ -449,7 +449,7 @@ class BUSCA:
             if img.dtype == np.uint8:
                 return img
             # already-normalised float crops (normalize_ims=False callers): map back to the u8 they came from
-            v = np.rint((img.astype(np.float64) * tracking._PIXEL_STD + tracking._PIXEL_MEAN) * 255.0)
+            v = np.rint((img.astype(np.float64) * crops._PIXEL_STD + crops._PIXEL_MEAN) * 255.0)
             return np.clip(v, 0, 255).astype(np.uint8)
 
         # normalize_ims=False: the caller's crops are already normalised floats and the reference pads with float 0.0 in

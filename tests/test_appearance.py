@@ -83,7 +83,9 @@ def test_symbol_declared_typed_and_exported():
         hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
         return set(re.findall(r"\b(busca_[a-z0-9_]+)\s*\(", hdr))
     assert declared("busca_appearance.h") == {"busca_appearance_cost"} == set(_lib.APPEARANCE_SIGNATURES)
-    for header, table in (("busca_hip.h", _lib.SIGNATURES), ("busca_assign.h", _lib.ASSIGN_SIGNATURES)):
+    for header, table in _lib.HEADERS.items():
+        if header == "busca_appearance.h":
+            continue
         assert "busca_appearance_cost" not in declared(header) and "busca_appearance_cost" not in table
     lib = _lib.load()
     fn = lib.busca_appearance_cost

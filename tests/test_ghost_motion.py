@@ -94,8 +94,9 @@ def test_symbols_declared_typed_and_exported():
         hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
         return set(re.findall(r"\b(busca_[a-z0-9_]+)\s*\(", hdr))
     assert declared("busca_ghost_motion.h") == set(NAMES) == set(_lib.GHOST_MOTION_SIGNATURES)
-    for header, table in (("busca_hip.h", _lib.SIGNATURES), ("busca_assign.h", _lib.ASSIGN_SIGNATURES), ("busca_appearance.h", _lib.APPEARANCE_SIGNATURES),
-                          ("busca_ghost.h", _lib.GHOST_SIGNATURES), ("busca_reid_bn.h", _lib.REID_BN_SIGNATURES)):
+    for header, table in _lib.HEADERS.items():
+        if header == "busca_ghost_motion.h":
+            continue
         assert not set(NAMES) & declared(header) and not set(NAMES) & set(table)
     lib = _lib.load()
     for name, nargs in NAMES.items():

@@ -66,7 +66,7 @@ def kernel_time(ctx, launch, reps):
 
 def main():
     import torch
-    from busca_amd import _lib, synth, tracking
+    from busca_amd import _lib, ghost, synth, tracking
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "ghost_bench.json")
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
     assert torch.cuda.is_available(), "ghost_bench needs a GPU"
@@ -107,7 +107,7 @@ def main():
             ta.append(t1 - t0); tb.append(t2 - t1)
         out = torch.empty(n, m, dtype=torch.float64, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream
-        code = tracking._GHOST_REDUCE[reduce]
+        code = ghost._GHOST_REDUCE[reduce]
         kt = kernel_time(ctx, lambda: ctx.check(lib.busca_ghost_distance(h, dg.data_ptr(), None, None, n, budget, dd.data_ptr(), m, E, code, out.data_ptr(), s)), reps)
         kmin = kernel_time(ctx, lambda: ctx.check(lib.busca_ghost_distance(h, dg.data_ptr(), None, None, n, budget, dd.data_ptr(), m, E, _lib.GHOST_MIN, out.data_ptr(), s)), reps)
         kapp = kernel_time(ctx, lambda: ctx.check(lib.busca_appearance_cost(h, dg.data_ptr(), None, None, n, budget, dd.data_ptr(), m, E, _lib.APPEAR_MIN, 0, out.data_ptr(), s)), reps)

@@ -54,7 +54,7 @@ def sequence(H, W, dev):
 
 def main():
     import torch
-    from busca_amd import _lib, tracking
+    from busca_amd import _lib, ecc, tracking
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "ghost_ecc_bench.json")
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 100
     assert torch.cuda.is_available(), "ghost_ecc_bench needs a GPU"
@@ -78,17 +78,17 @@ def main():
             norms.append(float(cam.norm))
         plane = torch.empty(H, W, dtype=torch.float32, device=dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        tracking._ecc_prepare(ctx, frames[0], 3, H, W, 15, plane)
+        ecc._ecc_prepare(ctx, frames[0], 3, H, W, 15, plane)
         torch.cuda.synchronize()
         e0.record()
         for r in range(reps):
-            tracking._ecc_prepare(ctx, frames[r % FRAMES], 3, H, W, 15, plane)
+            ecc._ecc_prepare(ctx, frames[r % FRAMES], 3, H, W, 15, plane)
         e1.record()
         e1.synchronize()
         prepare_us = e0.elapsed_time(e1) * 1e3 / reps
         planes = [torch.empty(H, W, dtype=torch.float32, device=dev) for _ in range(2)]
         for p, f in zip(planes, frames[:2]):
-            tracking._ecc_prepare(ctx, f, 3, H, W, 15, p)
+            ecc._ecc_prepare(ctx, f, 3, H, W, 15, p)
         per_iter = []
         for r in range(max(reps // 5, 5)):
             t = []
@@ -96,7 +96,7 @@ def main():
                 warp = np.eye(2, 3, dtype=np.float32)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                tracking._ecc_align_planes(ctx, planes[1], planes[0], _lib.ECC_EUCLIDEAN, n, -1.0, warp)
+                ecc._ecc_align_planes(ctx, planes[1], planes[0], _lib.ECC_EUCLIDEAN, n, -1.0, warp)
                 t.append(time.perf_counter() - t0)
             per_iter.append((t[1] - t[0]) / 19)
         t_down = []
