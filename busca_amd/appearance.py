@@ -150,12 +150,56 @@ class NearestNeighborDistanceMetric:
         self._gallery = new
         self._total = np.concatenate([self._total, np.zeros(ns - len(self._total), dtype=np.int64)])
 
-    def partial_fit(self, features, targets, active_targets):
+    def _fit_ema(self, features, targets, alpha, dev):
+        """partial_fit's EMA route: deep_sort/track.py:244-248 (and :85-87 for a target's first feature) in float32 tensor ops, in that order."""
+        f = to_dev(features, dev, torch.float32).reshape(len(targets), -1)
+        E = f.shape[1]
+        if self._gallery is not None and self._gallery.shape[2] != E:
+            raise ValueError("the gallery holds %d-dimensional samples, these have %d dimensions" % (self._gallery.shape[2], E))
+        for t in targets:
+            if t not in self._slot:
+                self._slot[t] = self._free.pop() if self._free else len(self._slot)
+        slots_needed = max(self._slot.values()) + 1
+        have_s = 0 if self._gallery is None else self._gallery.shape[0]
+        if slots_needed > have_s:
+            slots_needed = max(slots_needed, 2 * have_s, 16)
+        self._reserve(slots_needed, 1, E, dev)
+        ring = self._gallery.shape[1]
+        waves = []                                          # wave j: the (j+1)-th feature of every target of this call, so call order holds per target
+        seen = {}
+        for k, t in enumerate(targets):
+            j = seen.get(t, 0)
+            seen[t] = j + 1
+            if j == len(waves):
+                waves.append([])
+            s = self._slot[t]
+            tot = int(self._total[s])
+            waves[j].append((k, s, (tot - 1) % ring if tot else 0, int(tot > 0)))      # source, slot, ring row of its newest sample, whether it has one
+            self._total[s] = 1
+        table = torch.from_numpy(np.asarray([r for w in waves for r in w], dtype=np.int64).T.copy()).to(dev)      # one upload for every wave's index vectors
+        feature = f / torch.linalg.vector_norm(f, dim=1, keepdim=True)
+        lo = 0
+        for w in waves:
+            src, slot, old_row, has = table[:, lo:lo + len(w)]
+            lo += len(w)
+            feat = feature[src]
+            smooth = self._gallery[slot, old_row] * alpha + feat * (1 - alpha)      # two products and a sum, each rounded to float32
+            smooth = smooth / torch.linalg.vector_norm(smooth, dim=1, keepdim=True)
+            self._gallery[slot, torch.zeros_like(slot)] = torch.where((has != 0).unsqueeze(1), smooth, feat)
+
+    def partial_fit(self, features, targets, active_targets, ema_alpha=None):
         """Append feature k, L2-normalised (in float64, stored as float32; deep_sort/track.py:244 stores normalised features), to the samples of
-        targets[k]; keep each target's last `budget`; drop every target that is not in `active_targets` and free its slot."""
+        targets[k]; keep each target's last `budget`; drop every target that is not in `active_targets` and free its slot.
+        `ema_alpha` (StrongSORT's opt.EMA with opt.EMA_alpha, deep_sort/track.py:244-248): the target's slot holds ONE row instead.  With
+        feature = f / ||f||, a target that has a sample replaces it by smooth / ||smooth||, smooth = ema_alpha * old + (1 - ema_alpha) * feature; a
+        target without one stores feature (track.py:85-87).  Float32 tensor ops in that order on the device; `features` may be the device tensor
+        appearance_round was given.  Several features for one target in one call are applied in call order.  `budget` is ignored under EMA.
+        Use a metric with `ema_alpha` throughout or not at all (a gallery of several samples collapses to its newest one at the first EMA call)."""
         targets = list(np.asarray(targets).reshape(-1).tolist()) if not isinstance(targets, list) else targets
         dev = dev_of(self.ctx)
-        if len(targets):
+        if len(targets) and ema_alpha is not None:
+            self._fit_ema(features, targets, float(ema_alpha), dev)
+        elif len(targets):
             f = to_dev(features, dev, torch.float32).reshape(len(targets), -1).to(torch.float64)
             f = (f / torch.sqrt((f * f).sum(1, keepdim=True))).to(torch.float32)
             E = f.shape[1]

@@ -49,7 +49,8 @@ def ghost_proxies(gallery, mode="mean", window=0, slot=None, count=None, newest=
       newest   [S] ints or None: the ring row of every slot's newest sample (None: count - 1)
       mode     'last', 'first' (the oldest stored sample), 'mean', 'meannorm', 'median' (torch.median: the lower one)
       window   the newest `window` samples take part (tracker_cfg['avg_*']['num']); 0 or 'all', or more than a track has: all of them
-    torch.mode and the stateful 'mv_avg' are not built (mv_avg is `mv_avg * a + last * (1 - a)` on the caller's own tensor).
+    torch.mode and the stateful 'mv_avg' are not built here (mv_avg is `mv_avg * a + last * (1 - a)` on a per-track table: ghost_round runs it
+    on the table of GhostGallery.state).
     -> device float32 tensor [n,E]; a track without samples gets a row of NaN."""
     if mode in ("mode", "mv_avg"):
         raise NotImplementedError("ghost_proxies: the %r proxy is not built on the device (torch.mode has no kernel here; mv_avg is a stateful "
@@ -125,14 +126,64 @@ def _ghost_get(state, name, default=None):
     return state.get(name, default) if isinstance(state, dict) else getattr(state, name, default)
 
 
-def _ghost_proxy_rows(ctx, g, count, newest, slot, entry, what):
+def _ghost_mv_avg_table(state, entry, what):
+    """The (mv_avg, mv_seen) tensors of `state` for a group whose proxy is 'mv_avg'; refuses what cannot run before anything is written."""
+    table, seen = _ghost_get(state, "mv_avg"), _ghost_get(state, "mv_seen")
+    if table is None or seen is None:
+        raise NotImplementedError("ghost_round: %s proxy 'mv_avg' needs the per-track table `mv_avg` / `mv_seen` in `state`: build the state "
+                                  "with GhostGallery.state" % what)
+    if entry.get("num", "all") == "all":
+        raise ValueError("ghost_round: %s proxy 'mv_avg' takes a number as 'num': with 'all' the reference raises TypeError "
+                         "(mv_avg[i] * 'all', tracking_utils.py:88)" % what)
+    return table, seen
+
+
+def _ghost_mv_avg_rows(ctx, g, count, newest, slot, a, table, seen, num_active=None):
+    """get_proxy's 'mv_avg' branch (tracking_utils.py:83-89) on the state's own table: a track seen before gets mv_avg * a + last * (1 - a), a new
+    one its newest sample, and either way that vector becomes the track's mv_avg.  `a`: the weight of the group, or (a_act, a_inact) for the
+    first `num_active` rows and the others - one pass over both groups; the weights then ride in a float32 column, which holds what the scalar
+    operand of a float32 op is rounded to.  Float32 tensor ops in the reference's order - two products and one sum, each rounded, nothing that
+    may contract - so the bits are torch CPU's.  A row with a negative slot or without samples is NaN and leaves the table untouched.  No
+    synchronising call; the valid slots of a call are distinct."""
+    if not (torch.is_tensor(table) and torch.is_tensor(seen) and table.device == g.device and seen.device == g.device and table.dtype == torch.float32
+            and tuple(table.shape) == (g.shape[0], g.shape[2]) and tuple(seen.shape) == (g.shape[0],)):
+        raise ValueError("ghost_round: mv_avg / mv_seen must be the device tensors of GhostGallery.state: float32 [%d,%d] and [%d] flags"
+                         % (g.shape[0], g.shape[2], g.shape[0]))
+    last = ghost_proxies(g, "last", 0, slot=slot, count=count, newest=newest, ctx=ctx)
+    if isinstance(a, tuple):
+        wa, wb = (torch.full((slot.numel(), 1), v, dtype=torch.float32, device=g.device) for v in (a[1], 1 - a[1]))
+        wa[:num_active], wb[:num_active] = a[0], 1 - a[0]
+    else:
+        wa, wb = a, 1 - a
+    S = table.shape[0]
+    s = slot.long()
+    at = s.clamp(min=0)
+    ok = s >= 0
+    if count is not None:
+        ok = ok & (count[at] > 0)
+    f = torch.where((seen[at] != 0).unsqueeze(1), table[at] * wa + last * wb, last)
+    # the write-back through one spare row behind the table: skipped rows land there, so no valid slot is written twice and nothing is compacted on the host
+    to = torch.where(ok, s, S)
+    pad = torch.cat([table, table.new_zeros(1, table.shape[1])])
+    pad[to] = f
+    table.copy_(pad[:S])
+    flag = torch.cat([seen, seen.new_zeros(1)])
+    flag.index_fill_(0, to, 1)
+    seen.copy_(flag[:S])
+    return f
+
+
+def _ghost_proxy_rows(ctx, g, count, newest, slot, entry, what, state=None):
     """get_proxy's choice for one group of tracks (tracker_cfg['avg_act'] / ['avg_inact']) -> device [k,E] float32."""
     proxy, num = entry.get("proxy", "last"), entry.get("num", "all")
     if not entry.get("do", False) or proxy == "last":            # without 'do', track.feats: the newest sample
         mode, window = "last", 0
     elif num == "first":
         mode, window = "first", 0
-    elif proxy in ("mv_avg", "mode") or proxy not in _GHOST_PROXY:
+    elif proxy == "mv_avg":
+        table, seen = _ghost_mv_avg_table(state, entry, what)
+        return _ghost_mv_avg_rows(ctx, g, count, newest, slot, float(num), table, seen)
+    elif proxy == "mode" or proxy not in _GHOST_PROXY:
         raise NotImplementedError("ghost_round: %s proxy %r is not built on the device" % (what, proxy))
     else:
         mode, window = proxy, (0 if num == "all" else int(num))
@@ -143,7 +194,8 @@ def ghost_round(state, det_feats, labels=None, motion=None, cfg=None, sep=None, 
     """GHOST's association round without leaving the device: get_hungarian_each_sample / get_hungarian_with_proxy + solve_hungarian
     (adapters/GHOST/src/tracker.py:306-480) from the tracks' sample galleries and the detections' features in HBM to the matches on the host.
       state       the tracks: a dict or object with `gallery` [S,budget,E] float32 (host array or device tensor), `count` [S] and `newest` [S] (or None,
-                  as ghost_proxies), `slot` [n] or None - the gallery slot of track i, ACTIVE TRACKS FIRST - and `num_active`
+                  as ghost_proxies), `slot` [n] or None - the gallery slot of track i, ACTIVE TRACKS FIRST - and `num_active`; GhostGallery.state
+                  builds it, with the tables `mv_avg` [S,E] / `mv_seen` [S] the 'mv_avg' proxy reads AND UPDATES, once per group per call
       det_feats   [m,E] float32, host array or device tensor
       labels      (track_labels [n], det_labels [m]) or None; as in the reference only the each_sample route masks classes
       motion      [n,m] tracks x detections motion cost (host array or device tensor); needed when motion_config['apply_motion_model'],
@@ -188,7 +240,15 @@ def ghost_round(state, det_feats, labels=None, motion=None, cfg=None, sep=None, 
         if each:
             return ("samples", inact.get("num", 2)) if entry.get("do", False) else ("last",)
         return ("proxy", entry.get("proxy", "last"), entry.get("num", "all")) if entry.get("do", False) else ("last",)
+    for entry, what in ((act, "avg_act"), (inact, "avg_inact")):  # both groups' mv_avg entries are checked before either writes its table
+        if kind(entry)[:2] == ("proxy", "mv_avg") and entry.get("num", "all") != "first":
+            _ghost_mv_avg_table(state, entry, what)
     groups = ((0, n, inact, "avg_inact"),) if kind(act) == kind(inact) else ((0, na, act, "avg_act"), (na, n, inact, "avg_inact"))      # one launch where both groups run the same
+    if len(groups) == 2 and kind(act)[:2] == kind(inact)[:2] == ("proxy", "mv_avg") and "first" not in (act.get("num"), inact.get("num")):
+        # both groups blend, each with its own weight: one pass over all rows instead of two
+        rows = _ghost_mv_avg_rows(ctx, g, count, newest, slot, (float(act["num"]), float(inact["num"])), *_ghost_mv_avg_table(state, act, "avg_act"), num_active=na)
+        ghost_distance(rows, d, "min", out=app, ctx=ctx)
+        groups = ()
     for lo, hi, entry, what in groups:
         if hi == lo:
             continue
@@ -196,7 +256,7 @@ def ghost_round(state, det_feats, labels=None, motion=None, cfg=None, sep=None, 
             ghost_distance(g, d, inact.get("num", 2), slot=slot[lo:hi], count=count, out=app[lo:hi], ctx=ctx)
         else:                                                     # one vector per track (last_frame, or get_proxy), then the plain cosine distance
             entry = {"do": False} if each else entry
-            ghost_distance(_ghost_proxy_rows(ctx, g, count, newest, slot[lo:hi], entry, what), d, "min", out=app[lo:hi], ctx=ctx)
+            ghost_distance(_ghost_proxy_rows(ctx, g, count, newest, slot[lo:hi], entry, what, state), d, "min", out=app[lo:hi], ctx=ctx)
     tl = dl = None
     if each and labels is not None and cfg.get("nan_over_classes", True):
         tl, dl = labels
