@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so and libbusca_track.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -17,6 +17,12 @@ STAMP = OUT + ".flags"
 UNITS = [("busca_hip", True), ("busca_dt_f32", True), ("busca_dt_f16", True), ("busca_dt_x3", True), ("busca_dt_aux", False),
          ("busca_dtl_f32", True), ("busca_dtl_f16", True), ("busca_dtl_x3", True), ("busca_reid", True), ("busca_assign", False), ("busca_appear", False), ("busca_ghost", False), ("busca_ghost_motion", False)]
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+HEADERS = ["busca_hip.h", "busca_assign.h", "busca_appearance.h", "busca_ghost.h", "busca_ghost_motion.h", "busca_reid_bn.h", "busca_ecc.h"]
+# libbusca_track.so (include/busca_track.h): the context-free library of device-resident tracker state.  Its own units, objects, stamp and staleness
+# check; the same flags, no MFMA in it.  It shares kernel includes with busca_hip (track_kernel, pairwise_kernel), so an edit there rebuilds both.
+TRACK_OUT = os.path.join(HERE, "libbusca_track.so")
+TRACK_UNITS = [("busca_track", False)]
+TRACK_HEADERS = ["busca_track.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -74,32 +80,28 @@ def _compile(hipcc, unit, vgpr, used_line, verbose):
     raise RuntimeError("hipcc failed building %s.o:\n%s%s" % (unit, r.stdout, r.stderr))
 
 
-def build(force=False, verbose=False):
-    """(Re)build what is stale: a unit whose object is older than any file it includes, or everything when the library was built for another flag request
-    (sidecar stamp libbusca_hip.so.flags: line 1 = the request, line 2 = the flags that compiled - busca_build_info() returns line 2).  Without hipcc
+def _build_lib(out, units, headers, force, verbose):
+    """(Re)build one library: a unit whose object is older than any file it includes, or everything when the library was built for another flag request
+    (sidecar stamp <library>.flags: line 1 = the request, line 2 = the flags that compiled - busca_build_info() returns line 2).  Without hipcc
     (a GPU box that received the built library) an existing library is used as it is."""
+    stamp = out + ".flags"
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     have_hipcc = os.path.exists(hipcc)
-    stamp_ok = os.path.exists(STAMP) and open(STAMP).read().split("\n")[0] == _stamp_request()
+    stamp_ok = os.path.exists(stamp) and open(stamp).read().split("\n")[0] == _stamp_request()
     all_deps = set()
-    for unit, _ in UNITS:
+    for unit, _ in units:
         all_deps |= _deps(os.path.join(CSRC, unit + ".hip"))
-    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_hip.h"))
-    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_assign.h"))
-    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_appearance.h"))
-    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ghost.h"))
-    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ghost_motion.h"))
-    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_reid_bn.h"))
-    all_deps.add(os.path.join(os.path.dirname(HERE), "include", "busca_ecc.h"))
-    if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= _newest(all_deps) and (stamp_ok or not have_hipcc):
-        return OUT
+    for h in headers:
+        all_deps.add(os.path.join(os.path.dirname(HERE), "include", h))
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= _newest(all_deps) and (stamp_ok or not have_hipcc):
+        return out
     if not have_hipcc:
-        raise RuntimeError("%s is stale or missing and hipcc (%s) is not here" % (OUT, hipcc))
+        raise RuntimeError("%s is stale or missing and hipcc (%s) is not here" % (out, hipcc))
     os.makedirs(OBJ, exist_ok=True)
     want_vgpr = os.environ.get("BUSCA_NO_VGPR_FORM") is None
     used_line = " ".join(_requested_flags() + (VGPR_FORM if want_vgpr else []))
     stale = []
-    for unit, vgpr in UNITS:
+    for unit, vgpr in units:
         obj = os.path.join(OBJ, unit + ".o")
         if force or not stamp_ok or not os.path.exists(obj) or os.path.getmtime(obj) < _newest(_deps(os.path.join(CSRC, unit + ".hip"))):
             stale.append((unit, vgpr and want_vgpr))
@@ -111,17 +113,23 @@ def build(force=False, verbose=False):
     # the objects carry their device code already (no relocatable device code): a plain host link against the HIP runtime
     clang = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "lib", "llvm", "bin", "clang++")
     clang = clang if os.path.exists(clang) else "/opt/rocm/lib/llvm/bin/clang++"
-    cmd = [clang, "-shared", "-fPIC", "--hip-link", "--offload-arch=gfx950", "-o", OUT + ".tmp"] + [os.path.join(OBJ, u + ".o") for u, _ in UNITS]
+    cmd = [clang, "-shared", "-fPIC", "--hip-link", "--offload-arch=gfx950", "-o", out + ".tmp"] + [os.path.join(OBJ, u + ".o") for u, _ in units]
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("hipcc failed linking libbusca_hip.so")
-    os.replace(OUT + ".tmp", OUT)
-    with open(STAMP, "w") as f:
+        raise RuntimeError("hipcc failed linking %s" % os.path.basename(out))
+    os.replace(out + ".tmp", out)
+    with open(stamp, "w") as f:
         f.write(_stamp_request() + "\n" + used_line + "\n")
-    return OUT
+    return out
+
+
+def build(force=False, verbose=False):
+    """(Re)build what is stale of both libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
+    return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 
 if __name__ == "__main__":

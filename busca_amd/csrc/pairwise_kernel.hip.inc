@@ -12,6 +12,36 @@
 #define PW_TA 16
 #define PW_TB 64
 
+// bbox_overlaps of one pair, "+1" pixel convention (matching.py:53-91, cython_bbox)
+__device__ __forceinline__ double pairwise_iou(double ax1, double ay1, double ax2, double ay2, double bx1, double by1, double bx2, double by2) {
+#pragma clang fp contract(off)
+    const double iw = (ax2 < bx2 ? ax2 : bx2) - (ax1 > bx1 ? ax1 : bx1) + 1.0;
+    double iou = 0.0;
+    if (iw > 0) {
+        const double ih = (ay2 < by2 ? ay2 : by2) - (ay1 > by1 ? ay1 : by1) + 1.0;
+        if (ih > 0) {
+            const double area_a = (ax2 - ax1 + 1.0) * (ay2 - ay1 + 1.0);
+            const double area_b = (bx2 - bx1 + 1.0) * (by2 - by1 + 1.0);
+            const double inter = iw * ih;
+            const double ua = (area_a + area_b) - inter;
+            iou = inter / ua;
+        }
+    }
+    return iou;
+}
+
+// iou_distance of one pair and, with the detection's score (`score` not NULL), fuse_score (matching.py:173-186)
+__device__ __forceinline__ double pairwise_iou_cost(double iou, const double* __restrict__ score) {
+#pragma clang fp contract(off)
+    double v = 1.0 - iou;                                   // iou_distance
+    if (score != nullptr) {                                 // fuse_score: 1 - (1 - cost) * score
+        const double sim = 1.0 - v;
+        const double fs = sim * *score;
+        v = 1.0 - fs;
+    }
+    return v;
+}
+
 __global__ void __launch_bounds__(256) pairwise_kernel(const double* __restrict__ A, int nA, const double* __restrict__ Bx, int nB,
                                                        int mode, const double* __restrict__ scores, double* __restrict__ out) {
 #pragma clang fp contract(off)
@@ -45,27 +75,9 @@ __global__ void __launch_bounds__(256) pairwise_kernel(const double* __restrict_
                 v = v * w;
             }
         } else {
-            const double iw = (ax2 < bx2 ? ax2 : bx2) - (ax1 > bx1 ? ax1 : bx1) + 1.0;
-            double iou = 0.0;
-            if (iw > 0) {
-                const double ih = (ay2 < by2 ? ay2 : by2) - (ay1 > by1 ? ay1 : by1) + 1.0;
-                if (ih > 0) {
-                    const double area_a = (ax2 - ax1 + 1.0) * (ay2 - ay1 + 1.0);
-                    const double area_b = (bx2 - bx1 + 1.0) * (by2 - by1 + 1.0);
-                    const double inter = iw * ih;
-                    const double ua = (area_a + area_b) - inter;
-                    iou = inter / ua;
-                }
-            }
+            const double iou = pairwise_iou(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2);
             if (mode == BUSCA_PAIR_IOU) v = iou;
-            else {
-                v = 1.0 - iou;                                  // iou_distance
-                if (scores != nullptr) {                        // fuse_score: 1 - (1 - cost) * score
-                    const double sim = 1.0 - v;
-                    const double fs = sim * scores[j];
-                    v = 1.0 - fs;
-                }
-            }
+            else v = pairwise_iou_cost(iou, scores != nullptr ? scores + j : nullptr);
         }
         out[(size_t)i * nB + j] = v;
     }

@@ -21,15 +21,13 @@
 //  duplicate_mark_kernel : remove_duplicate_stracks, byte_tracker.py:685-698 - pairs with IoU cost < 0.15; the track with
 //      the shorter life (frame_id - start_frame) is dropped, ties drop the first list's track.
 
-__global__ void __launch_bounds__(64) kalman_predict_kernel(double* __restrict__ mean, double* __restrict__ cov, const uint8_t* __restrict__ not_tracked, int n) {
+// The per-track bodies below are what one 64-lane workgroup does for ONE track, given where that track's state lives: the kernels of this file index
+// the state by list position, the slot-indexed kernels of kalman_store_kernel.hip.inc by slot.  `tid`: the lane, 0 .. 63; every lane of the workgroup calls.
+__device__ __forceinline__ void kalman_predict_track(double* __restrict__ pm, double* __restrict__ pc, bool zero_vh, int tid) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x, tid = threadIdx.x;
-    if (t >= n) return;
     __shared__ double P[8][8], L[8][8], m[8];
-    double* pm = mean + (size_t)t * 8;
-    double* pc = cov + (size_t)t * 64;
     P[tid >> 3][tid & 7] = pc[tid];
-    if (tid < 8) m[tid] = (tid == 7 && not_tracked != nullptr && not_tracked[t]) ? 0.0 : pm[tid];
+    if (tid < 8) m[tid] = (tid == 7 && zero_vh) ? 0.0 : pm[tid];
     __syncthreads();
     const int i = tid >> 3, j = tid & 7;
     // left = F P : rows 0-3 add the velocity rows
@@ -49,6 +47,12 @@ __global__ void __launch_bounds__(64) kalman_predict_kernel(double* __restrict__
         v = v + 0.0;                                       // numpy adds the zero off-diagonal of motion_cov (-0.0 -> +0.0)
     pc[tid] = v;
     if (tid < 8) pm[tid] = tid < 4 ? m[tid] + m[tid + 4] : m[tid];
+}
+
+__global__ void __launch_bounds__(64) kalman_predict_kernel(double* __restrict__ mean, double* __restrict__ cov, const uint8_t* __restrict__ not_tracked, int n) {
+    const int t = blockIdx.x, tid = threadIdx.x;
+    if (t >= n) return;
+    kalman_predict_track(mean + (size_t)t * 8, cov + (size_t)t * 64, not_tracked != nullptr && not_tracked[t], tid);
 }
 
 // Lower Cholesky factor of the leading DIM x DIM block of S, column by column.  false: a pivot is not positive and finite.
@@ -80,14 +84,10 @@ __device__ __forceinline__ double kalman_innovation_var(int i, double h) {
     return sd * sd;
 }
 
-__global__ void __launch_bounds__(64) kalman_update_kernel(double* __restrict__ mean, double* __restrict__ cov, const double* __restrict__ meas, int n,
-                                                           int* __restrict__ status) {
+// `z`: the track's measurement [4];  `st`: its status word, or nullptr
+__device__ __forceinline__ void kalman_update_track(double* __restrict__ pm, double* __restrict__ pc, const double* __restrict__ z, int* __restrict__ st, int tid) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x, tid = threadIdx.x;
-    if (t >= n) return;
     __shared__ double P[8][8], Ss[4][4], K[8][4], KS[8][4], m[8], inn[4];
-    double* pm = mean + (size_t)t * 8;
-    double* pc = cov + (size_t)t * 64;
     P[tid >> 3][tid & 7] = pc[tid];
     if (tid < 8) m[tid] = pm[tid];
     __syncthreads();
@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(64) kalman_update_kernel(double* __restrict__ 
         const int i = tid >> 2, j = tid & 3;
         Ss[i][j] = P[i][j] + (i == j ? kalman_innovation_var(i, m[3]) : 0.0);
     } else if (tid < 20)
-        inn[tid - 16] = meas[(size_t)t * 4 + (tid - 16)] - m[tid - 16];
+        inn[tid - 16] = z[tid - 16] - m[tid - 16];
     __syncthreads();
     double S[4][4], L[4][4];
 #pragma unroll
@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(64) kalman_update_kernel(double* __restrict__ 
 #pragma unroll
         for (int j = 0; j < 4; ++j) S[i][j] = Ss[i][j];
     if (!kalman_cholesky<4>(S, L)) {                       // the same answer in every lane: the whole workgroup leaves
-        if (tid == 0 && status != nullptr) status[t] = 1;
+        if (tid == 0 && st != nullptr) *st = 1;
         return;
     }
     if (tid < 8) {                                         // row tid of the gain: S x = P[tid][:4]^T (cho_solve)
@@ -134,14 +134,18 @@ __global__ void __launch_bounds__(64) kalman_update_kernel(double* __restrict__ 
     const int i = tid >> 3, j = tid & 7;
     pc[tid] = P[i][j] - (((KS[i][0] * K[j][0] + KS[i][1] * K[j][1]) + KS[i][2] * K[j][2]) + KS[i][3] * K[j][3]);
     if (tid < 8) pm[tid] = m[tid] + (((inn[0] * K[tid][0] + inn[1] * K[tid][1]) + inn[2] * K[tid][2]) + inn[3] * K[tid][3]);
-    if (tid == 0 && status != nullptr) status[t] = 0;
+    if (tid == 0 && st != nullptr) *st = 0;
 }
 
-__global__ void __launch_bounds__(64) kalman_initiate_kernel(const double* __restrict__ meas, int n, double* __restrict__ mean, double* __restrict__ cov) {
-#pragma clang fp contract(off)
+__global__ void __launch_bounds__(64) kalman_update_kernel(double* __restrict__ mean, double* __restrict__ cov, const double* __restrict__ meas, int n,
+                                                           int* __restrict__ status) {
     const int t = blockIdx.x, tid = threadIdx.x;
     if (t >= n) return;
-    const double* z = meas + (size_t)t * 4;
+    kalman_update_track(mean + (size_t)t * 8, cov + (size_t)t * 64, meas + (size_t)t * 4, status != nullptr ? status + t : nullptr, tid);
+}
+
+__device__ __forceinline__ void kalman_initiate_track(const double* __restrict__ z, double* __restrict__ pm, double* __restrict__ pc, int tid) {
+#pragma clang fp contract(off)
     const int i = tid >> 3, j = tid & 7;
     double v = 0.0;
     if (i == j) {
@@ -153,23 +157,36 @@ __global__ void __launch_bounds__(64) kalman_initiate_kernel(const double* __res
         else sd = i < 4 ? (2 * wp) * h : (10 * wv) * h;    // 2 * w * h evaluates left to right in Python
         v = sd * sd;
     }
-    cov[(size_t)t * 64 + tid] = v;
-    if (tid < 8) mean[(size_t)t * 8 + tid] = tid < 4 ? z[tid] : 0.0;
+    pc[tid] = v;
+    if (tid < 8) pm[tid] = tid < 4 ? z[tid] : 0.0;
 }
 
-__global__ void __launch_bounds__(256) kalman_boxes_kernel(const double* __restrict__ mean, int n, int tlbr, double* __restrict__ out) {
-#pragma clang fp contract(off)
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+__global__ void __launch_bounds__(64) kalman_initiate_kernel(const double* __restrict__ meas, int n, double* __restrict__ mean, double* __restrict__ cov) {
+    const int t = blockIdx.x, tid = threadIdx.x;
     if (t >= n) return;
-    const double* pm = mean + t * 8;
+    kalman_initiate_track(meas + (size_t)t * 4, mean + (size_t)t * 8, cov + (size_t)t * 64, tid);
+}
+
+// STrack.tlwh (tlbr = 0) / STrack.tlbr of one state
+__device__ __forceinline__ void kalman_box_of(const double* __restrict__ pm, int tlbr, double (&o)[4]) {
+#pragma clang fp contract(off)
     const double h = pm[3];
     const double w = pm[2] * h;                            // ret[2] *= ret[3]
     const double x = pm[0] - w / 2, y = pm[1] - h / 2;     // ret[:2] -= ret[2:] / 2
-    double* o = out + t * 4;
     o[0] = x;
     o[1] = y;
     o[2] = tlbr ? w + x : w;                               // ret[2:] += ret[:2]
     o[3] = tlbr ? h + y : h;
+}
+
+__global__ void __launch_bounds__(256) kalman_boxes_kernel(const double* __restrict__ mean, int n, int tlbr, double* __restrict__ out) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    double b[4];
+    kalman_box_of(mean + t * 8, tlbr, b);
+    double* o = out + t * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = b[k];
 }
 
 #define KALMAN_GATE_TILE 256
@@ -194,15 +211,12 @@ __device__ __forceinline__ double kalman_gate_one(const double (&L)[4][4], const
     return s;
 }
 
-__global__ void __launch_bounds__(64) kalman_gating_kernel(const double* __restrict__ mean, const double* __restrict__ cov, int n,
-                                                           const double* __restrict__ meas, int m, int only_position, int metric,
-                                                           double* __restrict__ out, int* __restrict__ status) {
+// What every measurement of a track's gating row shares: the projected mean mu = mean[:4] and, for the Mahalanobis metric, the lower Cholesky factor
+// of S = P[:4,:4] + diag(std^2) - its leading 2 x 2 block with `only_position`.  false: S is not positive definite.
+__device__ __forceinline__ bool kalman_gate_factor(const double* __restrict__ pm, const double* __restrict__ pc, int only_position, int metric,
+                                                   double (&mu)[4], double (&L)[4][4]) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x, tid = threadIdx.x;
-    if (t >= n) return;
-    const double* pm = mean + (size_t)t * 8;
-    const double* pc = cov + (size_t)t * 64;
-    double mu[4], S[4][4], L[4][4];
+    double S[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         mu[i] = pm[i];
@@ -215,6 +229,17 @@ __global__ void __launch_bounds__(64) kalman_gating_kernel(const double* __restr
         for (int j = 0; j < 4; ++j) S[i][j] = pc[i * 8 + j] + (i == j ? kalman_innovation_var(i, mu[3]) : 0.0);
     bool ok = true;
     if (metric == 0) ok = only_position ? kalman_cholesky<2>(S, L) : kalman_cholesky<4>(S, L);
+    return ok;
+}
+
+__global__ void __launch_bounds__(64) kalman_gating_kernel(const double* __restrict__ mean, const double* __restrict__ cov, int n,
+                                                           const double* __restrict__ meas, int m, int only_position, int metric,
+                                                           double* __restrict__ out, int* __restrict__ status) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x, tid = threadIdx.x;
+    if (t >= n) return;
+    double mu[4], L[4][4];
+    const bool ok = kalman_gate_factor(mean + (size_t)t * 8, cov + (size_t)t * 64, only_position, metric, mu, L);
     if (blockIdx.y == 0 && tid == 0 && status != nullptr) status[t] = ok ? 0 : 1;
     for (int q = 0; q < KALMAN_GATE_TILE / 64; ++q) {
         const long j = (long)blockIdx.y * KALMAN_GATE_TILE + q * 64 + tid;

@@ -1,7 +1,8 @@
 """ByteTrack's Kalman filter for all tracks of a call at once: prediction, measurement update, initiation, gating distances, and the gated /
 blended cost matrix of an association round.  Fronts the busca_kalman_* entry points of include/busca_hip.h; restates
 adapters/ByteTrack/yolox/tracker/kalman_filter.py, matching.py:132-156 and byte_tracker.py:50-61,67,78,109,165-172.
-Tracks are objects with `.mean` [8], `.covariance` [8,8] and `.state`; every call makes one device->host copy."""
+Tracks are objects with `.mean` [8], `.covariance` [8,8] and `.state`; every call makes one device->host copy.  kalman_store.KalmanStore is the same
+filter on state that stays on the device."""
 import numpy as np
 import torch
 

@@ -1,0 +1,231 @@
+"""ByteTrack's Kalman state resident on the device: the means and covariances of all tracks stay in two device tensors over `capacity` slots, and
+every step names the slots it serves.  Fronts include/busca_track.h (libbusca_track.so, bound by _track_lib); restates what kalman.py restates -
+adapters/ByteTrack/yolox/tracker/kalman_filter.py, matching.py:132-186, byte_tracker.py:50-61,67,78,109,142-163 - without the objects: no state
+crosses PCIe in either direction, and the cost matrix of an association round is one launch."""
+import collections
+
+import numpy as np
+import torch
+
+from . import _track_lib, geometry
+from ._xfer import small_to_dev, stream_of
+from .assignment import _assign_dev, _empty_triple, _solved
+from .ghost_motion import _slots_checked
+from .kalman import _measurements, _raise_flagged, _set_states
+from .track_boxes import _tlbrs
+
+# the detections of a call on the device: tlbr [m,4], xyah [m,4], score [m] or None - views of one uploaded table
+DeviceDetections = collections.namedtuple("DeviceDetections", "tlbr xyah score m")
+
+
+def _small(x, dev, dtype):
+    """_xfer.small_to_dev; an empty table needs no staging."""
+    if not torch.is_tensor(x) and np.size(x) == 0:
+        return torch.empty(0, dtype=dtype, device=dev)
+    return small_to_dev(x, dev, dtype)
+
+
+class KalmanStore:
+    """The Kalman state of up to `capacity` tracks on the device (busca_track_kalman_*, busca_track_round_cost):
+      initiate(slots, dets)          KalmanFilter.initiate: STrack.activate's state of a new track - also how a slot is reused
+      predict(slots, not_tracked)    STrack.multi_predict in place
+      update(slots, dets, det_index) KalmanFilter.update in place -> device status words
+      boxes(slots)                   STrack.tlbr / tlwh
+      cost(slots, dets, ...)         the cost matrix of one association round, one launch -> (device [n,m], device status [n])
+      round(slots, dets, thresh)     predict, cost and the linear assignment -> (matches, u_track, u_detection); one small device->host copy
+      load / store(slots, stracks)   states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
+    `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors, allocated at the first call that needs them; the slot behind
+    the last is a spare no kernel writes (the kernels are told `capacity`), where load / store park the negative entries of a slot list.
+    Slot lists given as host lists or arrays are checked on the host - the entries >= 0 distinct and below `capacity`, ValueError otherwise; a negative
+    entry is skipped.  A slot list given as a device tensor is not read back: it is the caller's to keep distinct, and entries outside the capacity
+    are skipped by the kernels and touch no memory.  Detections: objects with `.tlwh` (and `.tlbr` for cost / round), a host [m,4] array or device
+    tensor of (x, y, a, h) measurements where only those are needed, or what detections() returned.  Every call is asynchronous on torch's
+    current stream of the device, except that round(), load() of nothing and store() wait for their one copy."""
+
+    def __init__(self, capacity, device=None):
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("KalmanStore(capacity=%d)" % capacity)
+        self.capacity = capacity
+        self.dev = torch.device("cuda", 0 if device is None else (device.index or 0) if isinstance(device, torch.device) else int(device))
+        self.mean = self.cov = None
+        self._lib = None
+
+    # ---- plumbing
+    def _state(self):
+        if self.mean is None:
+            self.mean = torch.zeros(self.capacity + 1, 8, dtype=torch.float64, device=self.dev)
+            self.cov = torch.zeros(self.capacity + 1, 8, 8, dtype=torch.float64, device=self.dev)
+        if self._lib is None:
+            self._lib = _track_lib.load()
+        return self._lib
+
+    def _slots(self, slots, what):
+        """-> (device i32 [n], n); a host list is checked first, before anything is allocated."""
+        slot, n = _slots_checked(slots, self.capacity, "KalmanStore." + what)
+        return _small(slot, self.dev, torch.int32), n
+
+    def _where(self):
+        return self.dev.index, stream_of(self.dev)
+
+    def detections(self, detections, det_scores=None, boxes=True):
+        """The detections of one or more calls in one upload -> DeviceDetections.  `detections`: objects with `.tlwh` and (`boxes`) `.tlbr`, or a host
+        [m,4] array of (x, y, a, h) measurements (then there are no boxes: enough for initiate and update)."""
+        if isinstance(detections, DeviceDetections):
+            return detections
+        if torch.is_tensor(detections):
+            z = detections.to(device=self.dev, dtype=torch.float64).contiguous().view(-1, 4)
+            return DeviceDetections(None, z, None, z.shape[0])
+        xyah = _measurements(detections)
+        m = xyah.shape[0]
+        boxes = boxes and not isinstance(detections, np.ndarray)
+        if m == 0:
+            none = torch.empty(0, 4, dtype=torch.float64, device=self.dev)
+            return DeviceDetections(none if boxes else None, none, None, 0)
+        parts = [xyah.reshape(-1)]
+        if boxes:
+            parts.append(_tlbrs(detections).reshape(-1))
+        if det_scores is not None:
+            sc = np.asarray(det_scores, dtype=np.float64).reshape(-1)
+            if len(sc) != m:
+                raise ValueError("KalmanStore: %d scores for %d detections" % (len(sc), m))
+            parts.append(sc)
+        table = small_to_dev(np.concatenate(parts), self.dev, torch.float64)
+        score_at = 8 * m if boxes else 4 * m
+        return DeviceDetections(table[4 * m:8 * m].view(m, 4) if boxes else None, table[:4 * m].view(m, 4),
+                                table[score_at:score_at + m] if det_scores is not None else None, m)
+
+    def _pairs(self, slots, detections, det_index, what):
+        slot, n = self._slots(slots, what)
+        det = self.detections(detections, boxes=False)
+        idx = None
+        if det_index is not None:
+            idx = _small(det_index if torch.is_tensor(det_index) else np.asarray(det_index, dtype=np.int32), self.dev, torch.int32)
+            if idx.numel() != n:
+                raise ValueError("KalmanStore.%s: %d detection indices for %d slots" % (what, idx.numel(), n))
+        elif n > det.m:
+            raise ValueError("KalmanStore.%s: %d slots for %d detections" % (what, n, det.m))
+        return slot, n, det, idx
+
+    # ---- the filter
+    def initiate(self, slots, detections, det_index=None):
+        """KalmanFilter.initiate of detection det_index[i] (None: i) into slot slots[i]: a new track, or a new tenant of an abandoned slot."""
+        slot, n, det, idx = self._pairs(slots, detections, det_index, "initiate")
+        if n == 0:
+            return
+        lib = self._state()
+        _track_lib.check(lib.busca_track_kalman_initiate(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, det.xyah.data_ptr(),
+                                                         None if idx is None else idx.data_ptr(), det.m, *self._where()))
+
+    def predict(self, slots, not_tracked=None):
+        """STrack.multi_predict of the listed slots in place; not_tracked[i] true: mean[7] of that track is zeroed first (state != Tracked)."""
+        slot, n = self._slots(slots, "predict")
+        self._predict(slot, n, not_tracked)
+
+    def _predict(self, slot, n, not_tracked):
+        nt = None
+        if not_tracked is not None:
+            nt = _small(not_tracked if torch.is_tensor(not_tracked) else np.asarray(not_tracked, dtype=np.bool_).astype(np.uint8), self.dev, torch.uint8)
+            if nt.numel() != n:
+                raise ValueError("KalmanStore.predict: %d `not_tracked` flags for %d slots" % (nt.numel(), n))
+        if n == 0:
+            return
+        lib = self._state()
+        _track_lib.check(lib.busca_track_kalman_predict(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(),
+                                                        None if nt is None else nt.data_ptr(), n, *self._where()))
+
+    def update(self, slots, detections, det_index=None):
+        """KalmanFilter.update of slot slots[i] with detection det_index[i] (None: i), in place -> device int32 [n] status words: 1 where the
+        reference raises LinAlgError (that slot keeps its state), which is the caller's to read or not."""
+        slot, n, det, idx = self._pairs(slots, detections, det_index, "update")
+        status = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if n == 0:
+            return status
+        lib = self._state()
+        _track_lib.check(lib.busca_track_kalman_update(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, det.xyah.data_ptr(),
+                                                       None if idx is None else idx.data_ptr(), det.m, status.data_ptr(), *self._where()))
+        return status
+
+    def boxes(self, slots, tlbr=True):
+        """STrack.tlbr (tlwh with tlbr=False) of the listed slots -> device float64 [n,4]; a skipped entry: a row of NaN."""
+        slot, n = self._slots(slots, "boxes")
+        out = torch.empty(n, 4, dtype=torch.float64, device=self.dev)
+        if n == 0:
+            return out
+        lib = self._state()
+        _track_lib.check(lib.busca_track_kalman_boxes(self.mean.data_ptr(), self.capacity, slot.data_ptr(), n, int(bool(tlbr)), out.data_ptr(), *self._where()))
+        return out
+
+    # ---- association
+    def cost(self, slots, detections, det_scores=None, fuse_motion=False, only_position=False, lambda_=0.98, gate_only=False):
+        """The cost matrix of one association round from the states as they are (after predict): iou_distance of the tracks' boxes, fuse_score with
+        `det_scores`, matching.fuse_motion with `fuse_motion` (`gate_only`: gate_cost_matrix, no blend) -> (device float64 [n,m], device int32 [n]
+        status words: 1 where the projected covariance is not positive definite, that row being NaN).  A skipped slot: a row of +inf.  One launch."""
+        slot, n = self._slots(slots, "cost")
+        return self._cost(slot, n, self.detections(detections, det_scores), fuse_motion, only_position, lambda_, gate_only)
+
+    def _cost(self, slot, n, det, fuse_motion, only_position, lambda_, gate_only=False):
+        if fuse_motion and gate_only:
+            raise ValueError("KalmanStore.cost: fuse_motion and gate_only exclude each other")
+        if det.tlbr is None:
+            raise ValueError("KalmanStore.cost: the detections carry no boxes (objects with .tlbr and .tlwh are needed)")
+        out = torch.empty(n, det.m, dtype=torch.float64, device=self.dev)
+        if n == 0 or det.m == 0:
+            return out, torch.zeros(n, dtype=torch.int32, device=self.dev)
+        status = torch.empty(n, dtype=torch.int32, device=self.dev)
+        flags = (_track_lib.FUSE_MOTION if fuse_motion else 0) | (_track_lib.GATE_ONLY if gate_only else 0)
+        if flags and only_position:
+            flags |= _track_lib.ONLY_POSITION
+        lib = self._state()
+        _track_lib.check(lib.busca_track_round_cost(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, det.tlbr.data_ptr(),
+                                                    det.xyah.data_ptr(), None if det.score is None else det.score.data_ptr(), det.m, flags, float(lambda_),
+                                                    out.data_ptr(), status.data_ptr(), *self._where()))
+        return out, status
+
+    def round(self, slots, detections, thresh, det_scores=None, fuse_motion=False, only_position=False, lambda_=0.98, not_tracked=None, predict=True):
+        """One whole association round, assignment.associate_round on resident state: predict (unless `predict` is false: the states are predicted
+        already), the cost matrix, linear_assignment(cost, thresh) -> (matches, u_track, u_detection) with rows indexing `slots`.  Three launches;
+        ONE device->host copy of n + m + 1 match words and n status words - no state and no matrix crosses.  Raises LinAlgError where
+        associate_round does, after the prediction of every listed track."""
+        slot, n = self._slots(slots, "round")
+        det = self.detections(detections, det_scores)
+        if predict:
+            self._predict(slot, n, not_tracked)
+        if n == 0 or det.m == 0:
+            return _empty_triple(n, det.m)
+        cost, status = self._cost(slot, n, det, fuse_motion, only_position, lambda_)
+        sol = _assign_dev(geometry.default_context(self.dev.index), cost, 1, n, det.m, thresh)
+        host = torch.cat([sol.view(-1), status]).cpu().numpy()
+        _raise_flagged(host[n + det.m + 1:], "KalmanStore.round")
+        return _solved(host[:n + det.m + 1].astype(np.int64), n, det.m, "KalmanStore.round")
+
+    # ---- objects in and out
+    def _rows(self, slots, stracks, what):
+        slot, n = _slots_checked(slots, self.capacity, "KalmanStore." + what)
+        if torch.is_tensor(slot):
+            raise ValueError("KalmanStore.%s takes a host slot list" % what)
+        if n != len(stracks):
+            raise ValueError("KalmanStore.%s: %d slots for %d tracks" % (what, n, len(stracks)))
+        return np.where(slot < 0, self.capacity, slot).astype(np.int64), n      # negative entries: the spare slot
+
+    def load(self, slots, stracks):
+        """The states of objects with `.mean` [8] / `.covariance` [8,8] into their slots (one upload)."""
+        rows, n = self._rows(slots, stracks, "load")
+        if n == 0:
+            return
+        self._state()
+        table = np.concatenate([np.asarray([st.mean for st in stracks], dtype=np.float64).reshape(-1),
+                                np.asarray([st.covariance for st in stracks], dtype=np.float64).reshape(-1)])
+        table = small_to_dev(table, self.dev, torch.float64)
+        rows = small_to_dev(rows, self.dev, torch.int64)
+        self.mean.index_copy_(0, rows, table[:8 * n].view(n, 8))
+        self.cov.index_copy_(0, rows, table[8 * n:].view(n, 8, 8))
+
+    def store(self, slots, stracks):
+        """The states of the listed slots into the objects' `.mean` / `.covariance` (one device->host copy)."""
+        rows, n = self._rows(slots, stracks, "store")
+        if n == 0:
+            return
+        self._state()
+        rows = small_to_dev(rows, self.dev, torch.int64)
+        _set_states(stracks, torch.cat([self.mean.index_select(0, rows).view(-1), self.cov.index_select(0, rows).view(-1)]).cpu().numpy())
