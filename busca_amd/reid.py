@@ -97,6 +97,22 @@ class ReIDEncoderHIP:
         assert crops_u8.dtype == torch.uint8 and tuple(crops_u8.shape[1:]) == (384, 128, 3), crops_u8.shape
         return dev, crops_u8
 
+    def _flags(self, zero_norm, n, dev, stream):
+        """`zero_norm` as the kernels read it: n bytes on the context's device (or None).  A cuda uint8 / bool tensor of shape [n] on that device passes as it
+        is - no copy, no synchronising call; a numpy array or a sequence of n flags is staged on the stream of the call (h2d_async); the caller keeps the result
+        alive until the pass is enqueued.  Anything else - another dtype, shape or device, a host tensor - would be read as bytes that are not there: ValueError."""
+        if zero_norm is None:
+            return None
+        if torch.is_tensor(zero_norm):
+            if zero_norm.dtype not in (torch.uint8, torch.bool) or tuple(zero_norm.shape) != (n,) or zero_norm.device != dev or not zero_norm.is_contiguous():
+                raise ValueError("zero_norm: a contiguous uint8 / bool tensor of shape (%d,) on %s (or a numpy array / sequence of %d flags), not %s %s on %s"
+                                 % (n, dev, n, zero_norm.dtype, tuple(zero_norm.shape), zero_norm.device))
+            return zero_norm
+        flags = np.asarray(zero_norm)
+        if flags.dtype.kind not in "bui" or flags.shape != (n,):
+            raise ValueError("zero_norm: %d flags (bool / integer), not %s %s" % (n, flags.dtype, flags.shape))
+        return geometry.h2d_async((flags != 0).astype(np.uint8), dev, stream)
+
     def forward_running(self, crops_u8, output="plain", stream=None, zero_norm=None):
         """Eval-mode forward: BatchNorm on the running statistics, so crop i's features depend on crop i alone.  `output`: "plain" (L2-normalised, as
         `forward`), "norm" (fc7 as it is) or "neck" (= "norm": the encoder has no neck)."""
@@ -105,7 +121,8 @@ class ReIDEncoderHIP:
         n = crops_u8.shape[0]
         feats = torch.empty(n, 512, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        self.ctx.check(self.ctx.lib.busca_reid_forward_running(self.ctx.h, crops_u8.data_ptr(), n, _ptr(zero_norm), OUTPUTS[output], feats.data_ptr(), s))
+        zn = self._flags(zero_norm, n, dev, stream)
+        self.ctx.check(self.ctx.lib.busca_reid_forward_running(self.ctx.h, crops_u8.data_ptr(), n, _ptr(zn), OUTPUTS[output], feats.data_ptr(), s))
         return feats
 
     def adapt(self, crops_u8, momentum, output="plain", stream=None, zero_norm=None):
@@ -117,7 +134,8 @@ class ReIDEncoderHIP:
         n = crops_u8.shape[0]
         feats = torch.empty(n, 512, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        self.ctx.check(self.ctx.lib.busca_reid_adapt(self.ctx.h, crops_u8.data_ptr(), n, _ptr(zero_norm), float(momentum), OUTPUTS[output], feats.data_ptr(), s))
+        zn = self._flags(zero_norm, n, dev, stream)
+        self.ctx.check(self.ctx.lib.busca_reid_adapt(self.ctx.h, crops_u8.data_ptr(), n, _ptr(zn), float(momentum), OUTPUTS[output], feats.data_ptr(), s))
         if float(momentum) != 0.0 and n > 0:
             self._running_dirty = True
         return feats
@@ -142,7 +160,7 @@ class ReIDEncoderHIP:
         self.ctx.check(self.ctx.lib.busca_reid_reserve(self.ctx.h, int(n), s))
 
     def forward(self, crops_u8, stream=None, zero_norm=None, weights=None):
-        """`zero_norm` (cuda u8 [n] or None): crops flagged 1 are 0.0 after normalisation (busca_reid_forward_ex).
+        """`zero_norm` (cuda u8 / bool [n], a numpy array / sequence of n flags, or None; `_flags`): crops flagged 1 are 0.0 after normalisation (busca_reid_forward_ex).
         `weights` (numpy / sequence of n multiplicities, or None): crop i stands for weights[i] identical crops of the BatchNorm
         batch - each distinct crop is computed once, the batch statistics count it weights[i] times (busca_reid_forward_w)."""
         self._ensure_loaded()
@@ -154,7 +172,7 @@ class ReIDEncoderHIP:
         n = crops_u8.shape[0]
         feats = torch.empty(n, 512, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        zn = zero_norm.data_ptr() if zero_norm is not None else None
+        zn = self._flags(zero_norm, n, dev, stream)
         wd, wsum = None, 0.0
         if weights is not None and not (np.asarray(weights) != 1).any():
             weights = None                      # every crop once: the plain forward (same schedule, bit for bit)
@@ -163,5 +181,5 @@ class ReIDEncoderHIP:
             assert w.shape == (n,) and (w >= 1).all()
             wsum = float(w.astype(np.float64).sum())
             wd = geometry.h2d_async(w, dev, stream)     # ordered on the stream the pass runs on
-        self.ctx.check(self.ctx.lib.busca_reid_forward_w(self.ctx.h, crops_u8.data_ptr(), n, zn, _ptr(wd), wsum, feats.data_ptr(), s))
+        self.ctx.check(self.ctx.lib.busca_reid_forward_w(self.ctx.h, crops_u8.data_ptr(), n, _ptr(zn), _ptr(wd), wsum, feats.data_ptr(), s))
         return feats
