@@ -5,8 +5,8 @@ Tracker._match's first stage (deep_sort/tracker.py:211-236).  nn_matching.py is 
 import numpy as np
 import torch
 
-from . import _lib, geometry
-from ._xfer import dev_of, stream_of, to_dev
+from . import _lib, _store_lib, geometry
+from ._xfer import dev_of, small_to_dev, stream_of, to_dev
 from .assignment import _assign_dev, _solved
 from .kalman import _download_with_status, _gate_dev, _gating_dev, _measurements, _raise_flagged, _upload_states
 from .track_boxes import _tlbrs
@@ -151,7 +151,9 @@ class NearestNeighborDistanceMetric:
         self._total = np.concatenate([self._total, np.zeros(ns - len(self._total), dtype=np.int64)])
 
     def _fit_ema(self, features, targets, alpha, dev):
-        """partial_fit's EMA route: deep_sort/track.py:244-248 (and :85-87 for a target's first feature) in float32 tensor ops, in that order."""
+        """partial_fit's EMA route: deep_sort/track.py:244-248 (and :85-87 for a target's first feature) as one busca_store_ema_fit launch
+        (include/busca_store.h) on torch's current stream.  The host groups the call's features by target - one upload of the group table - and
+        one workgroup per target applies its features in call order, so a target fed several times costs no further launch."""
         f = to_dev(features, dev, torch.float32).reshape(len(targets), -1)
         E = f.shape[1]
         if self._gallery is not None and self._gallery.shape[2] != E:
@@ -164,35 +166,29 @@ class NearestNeighborDistanceMetric:
         if slots_needed > have_s:
             slots_needed = max(slots_needed, 2 * have_s, 16)
         self._reserve(slots_needed, 1, E, dev)
-        ring = self._gallery.shape[1]
-        waves = []                                          # wave j: the (j+1)-th feature of every target of this call, so call order holds per target
-        seen = {}
+        S, ring = self._gallery.shape[:2]
+        groups = {}                                         # slot -> [ring row of the sample it has or -1, the rows of `features` for it in call order]
         for k, t in enumerate(targets):
-            j = seen.get(t, 0)
-            seen[t] = j + 1
-            if j == len(waves):
-                waves.append([])
             s = self._slot[t]
-            tot = int(self._total[s])
-            waves[j].append((k, s, (tot - 1) % ring if tot else 0, int(tot > 0)))      # source, slot, ring row of its newest sample, whether it has one
-            self._total[s] = 1
-        table = torch.from_numpy(np.asarray([r for w in waves for r in w], dtype=np.int64).T.copy()).to(dev)      # one upload for every wave's index vectors
-        feature = f / torch.linalg.vector_norm(f, dim=1, keepdim=True)
-        lo = 0
-        for w in waves:
-            src, slot, old_row, has = table[:, lo:lo + len(w)]
-            lo += len(w)
-            feat = feature[src]
-            smooth = self._gallery[slot, old_row] * alpha + feat * (1 - alpha)      # two products and a sum, each rounded to float32
-            smooth = smooth / torch.linalg.vector_norm(smooth, dim=1, keepdim=True)
-            self._gallery[slot, torch.zeros_like(slot)] = torch.where((has != 0).unsqueeze(1), smooth, feat)
+            if s not in groups:
+                tot = int(self._total[s])
+                groups[s] = [(tot - 1) % ring if tot else -1, []]
+                self._total[s] = 1
+            groups[s][1].append(k)
+        start = np.cumsum([0] + [len(ks) for _, ks in groups.values()])
+        g, k = len(groups), len(targets)
+        table = small_to_dev(np.concatenate([list(groups), [old for old, _ in groups.values()], start, [j for _, ks in groups.values() for j in ks]])
+                             .astype(np.int32), dev, torch.int32)      # one upload: group_slot [g], group_old_row [g], group_start [g + 1], src [k]
+        _store_lib.check(_store_lib.load().busca_store_ema_fit(
+            self._gallery.data_ptr(), S, ring, E, f.data_ptr(), k, table.data_ptr(), table[g:].data_ptr(), table[2 * g:].data_ptr(),
+            table[3 * g + 1:].data_ptr(), g, k, alpha, dev.index, stream_of(dev)))
 
     def partial_fit(self, features, targets, active_targets, ema_alpha=None):
         """Append feature k, L2-normalised (in float64, stored as float32; deep_sort/track.py:244 stores normalised features), to the samples of
         targets[k]; keep each target's last `budget`; drop every target that is not in `active_targets` and free its slot.
         `ema_alpha` (StrongSORT's opt.EMA with opt.EMA_alpha, deep_sort/track.py:244-248): the target's slot holds ONE row instead.  With
         feature = f / ||f||, a target that has a sample replaces it by smooth / ||smooth||, smooth = ema_alpha * old + (1 - ema_alpha) * feature; a
-        target without one stores feature (track.py:85-87).  Float32 tensor ops in that order on the device; `features` may be the device tensor
+        target without one stores feature (track.py:85-87).  Float32 in that order, one busca_store_ema_fit launch; `features` may be the device tensor
         appearance_round was given.  Several features for one target in one call are applied in call order.  `budget` is ignored under EMA.
         Use a metric with `ema_alpha` throughout or not at all (a gallery of several samples collapses to its newest one at the first EMA call)."""
         targets = list(np.asarray(targets).reshape(-1).tolist()) if not isinstance(targets, list) else targets

@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so and libbusca_track.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so and libbusca_store.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -23,6 +23,11 @@ HEADERS = ["busca_hip.h", "busca_assign.h", "busca_appearance.h", "busca_ghost.h
 TRACK_OUT = os.path.join(HERE, "libbusca_track.so")
 TRACK_UNITS = [("busca_track", False)]
 TRACK_HEADERS = ["busca_track.h", "busca_hip.h"]
+# libbusca_store.so (include/busca_store.h): the context-free library of device-resident appearance state.  Handled exactly as the track library; it
+# shares no kernel text with the other two.
+STORE_OUT = os.path.join(HERE, "libbusca_store.so")
+STORE_UNITS = [("busca_store", False)]
+STORE_HEADERS = ["busca_store.h"]
 
 
 def _requested_flags():
@@ -127,8 +132,9 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of both libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the three libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
+    _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

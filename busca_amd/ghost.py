@@ -4,7 +4,7 @@ tracking_utils.py:63-126 (get_proxy) and base_tracker.py:101-106,495-531,713-731
 import numpy as np
 import torch
 
-from . import _lib, geometry
+from . import _lib, _store_lib, geometry
 from ._xfer import stream_of, to_dev
 from .appearance import _check_width, gallery_operands
 from .assignment import _assign_dev
@@ -141,36 +141,22 @@ def _ghost_mv_avg_table(state, entry, what):
 def _ghost_mv_avg_rows(ctx, g, count, newest, slot, a, table, seen, num_active=None):
     """get_proxy's 'mv_avg' branch (tracking_utils.py:83-89) on the state's own table: a track seen before gets mv_avg * a + last * (1 - a), a new
     one its newest sample, and either way that vector becomes the track's mv_avg.  `a`: the weight of the group, or (a_act, a_inact) for the
-    first `num_active` rows and the others - one pass over both groups; the weights then ride in a float32 column, which holds what the scalar
-    operand of a float32 op is rounded to.  Float32 tensor ops in the reference's order - two products and one sum, each rounded, nothing that
-    may contract - so the bits are torch CPU's.  A row with a negative slot or without samples is NaN and leaves the table untouched.  No
-    synchronising call; the valid slots of a call are distinct."""
+    first `num_active` rows and the others - one pass over both groups.  One busca_store_mv_avg launch on torch's current stream (include/
+    busca_store.h): it reads the newest ring row itself and blends in float32 in the reference's order - two products and one sum, each rounded,
+    nothing contracted, the weights (float)a and (float)(1 - a) as torch forms them from a Python scalar - so the bits are torch CPU's.  A row with
+    a skipped slot or without samples is NaN and leaves the table untouched.  No synchronising call; the valid slots of a call are distinct."""
     if not (torch.is_tensor(table) and torch.is_tensor(seen) and table.device == g.device and seen.device == g.device and table.dtype == torch.float32
-            and tuple(table.shape) == (g.shape[0], g.shape[2]) and tuple(seen.shape) == (g.shape[0],)):
+            and tuple(table.shape) == (g.shape[0], g.shape[2]) and tuple(seen.shape) == (g.shape[0],)
+            and seen.dtype in (torch.uint8, torch.bool) and table.is_contiguous() and seen.is_contiguous()):
         raise ValueError("ghost_round: mv_avg / mv_seen must be the device tensors of GhostGallery.state: float32 [%d,%d] and [%d] flags"
                          % (g.shape[0], g.shape[2], g.shape[0]))
-    last = ghost_proxies(g, "last", 0, slot=slot, count=count, newest=newest, ctx=ctx)
-    if isinstance(a, tuple):
-        wa, wb = (torch.full((slot.numel(), 1), v, dtype=torch.float32, device=g.device) for v in (a[1], 1 - a[1]))
-        wa[:num_active], wb[:num_active] = a[0], 1 - a[0]
-    else:
-        wa, wb = a, 1 - a
-    S = table.shape[0]
-    s = slot.long()
-    at = s.clamp(min=0)
-    ok = s >= 0
-    if count is not None:
-        ok = ok & (count[at] > 0)
-    f = torch.where((seen[at] != 0).unsqueeze(1), table[at] * wa + last * wb, last)
-    # the write-back through one spare row behind the table: skipped rows land there, so no valid slot is written twice and nothing is compacted on the host
-    to = torch.where(ok, s, S)
-    pad = torch.cat([table, table.new_zeros(1, table.shape[1])])
-    pad[to] = f
-    table.copy_(pad[:S])
-    flag = torch.cat([seen, seen.new_zeros(1)])
-    flag.index_fill_(0, to, 1)
-    seen.copy_(flag[:S])
-    return f
+    n = slot.numel()
+    a_act, a_inact = a if isinstance(a, tuple) else (a, a)
+    out = torch.empty(n, g.shape[2], dtype=torch.float32, device=g.device)
+    _store_lib.check(_store_lib.load().busca_store_mv_avg(
+        g.data_ptr(), _lib.ptr(count), _lib.ptr(newest), table.data_ptr(), seen.data_ptr(), g.shape[0], g.shape[1], g.shape[2], slot.data_ptr(), n,
+        n if num_active is None else int(num_active), float(a_act), float(a_inact), out.data_ptr(), g.device.index, stream_of(g.device)))
+    return out
 
 
 def _ghost_proxy_rows(ctx, g, count, newest, slot, entry, what, state=None):

@@ -1,28 +1,17 @@
 """GHOST's appearance state on the device: per track slot a ring of the newest features and the moving-average proxy, kept where ghost_round reads
-them.  Fronts no header: ring writes are device tensor ops on torch's current stream, the reads are busca_ghost_proxies / busca_ghost_distance
-(include/busca_ghost.h) through ghost_round.  Restates Track.__init__ / add_detection's feature bookkeeping
+them.  Fronts include/busca_store.h (libbusca_store.so, bound by _store_lib): a ring write is one busca_store_ring_add launch, a release one
+busca_store_release launch, on torch's current stream; the reads are busca_ghost_proxies / busca_ghost_distance (include/busca_ghost.h) and
+busca_store_mv_avg through ghost_round.  Restates Track.__init__ / add_detection's feature bookkeeping
 (adapters/GHOST/src/tracking_utils.py:286-289, 342-343) and the reset of tracks beyond their patience (adapters/GHOST/src/tracker.py:252-255)."""
 import numpy as np
 import torch
 
-from . import geometry
-from ._xfer import small_to_dev, to_dev
+from . import _store_lib, geometry
+from ._lib import ptr
+from ._xfer import h2d_async, small_to_dev, stream_of, to_dev
 from .ghost_motion import _slots_checked
 
-
-def _ring_append(gallery, count, newest, seen, slot, rows, new):
-    """The ring rule on tensors that carry one spare slot behind the last: rows[i] becomes the newest sample of slot[i] (int64; negative entries
-    go to the spare slot, whose contents mean nothing).  new[i] (bool or None) empties the slot first.  No synchronising call."""
-    spare, budget = gallery.shape[0] - 1, gallery.shape[1]
-    s = torch.where(slot < 0, spare, slot)
-    c = count[s]
-    if new is not None:
-        c = torch.where(new, torch.zeros_like(c), c)
-        seen[s] = torch.where(new, torch.zeros_like(seen[s]), seen[s])
-    row = torch.where(c == 0, torch.zeros_like(c), (newest[s] + 1) % budget)
-    gallery[s, row.long()] = rows
-    newest[s] = row
-    count[s] = torch.clamp(c + 1, max=budget)
+_FLAG_DTYPES = (torch.uint8, torch.bool)
 
 
 class GhostGallery:
@@ -32,13 +21,16 @@ class GhostGallery:
       release(slots)             the track is gone (or beyond patience + 5, where the reference empties past_feats): the slot can be reused
       state(active, inactive)    the dict ghost_round takes, ACTIVE TRACKS FIRST
     gallery [capacity,budget,E] float32, count / newest [capacity] int32, mv_avg [capacity,E] float32, mv_seen [capacity] uint8 are device tensors
-    (views of storage with one spare slot behind the last, where the writes of skipped entries land).  The ring row of a new sample is 0 for an
-    empty slot, else (newest + 1) % budget; count = min(count + 1, budget).  Features are stored as given: GHOST does not normalise them.
+    (views of storage with one spare slot behind the last, which no kernel is told of or writes: a skipped entry touches no memory).  The ring row
+    of a new sample is 0 for an empty slot, else (newest + 1) % budget; count = min(count + 1, budget).  Features are stored as given: GHOST does
+    not normalise them.
     The reference keeps every sample; this keeps `budget` rows, which is the same for windows num <= budget or tracks no longer than that; 'first'
     means the oldest sample still stored.  A GhostMotion of the same capacity shares the slots: state(..., motion=) hands it to ghost_round.
     Slot lists given as host lists or arrays are checked on the host - the entries >= 0 distinct and below `capacity`, ValueError otherwise,
-    negative entries skipped.  A slot list given as a device tensor is not read back: it is the caller's to keep distinct and below `capacity`
-    (negative entries are skipped).  Everything is ordered on torch's current stream; with all operands on the device no call synchronises."""
+    negative entries skipped.  A slot list given as a device tensor is not read back: it is the caller's to keep distinct (entries that are
+    negative or beyond `capacity` are skipped).  Device operands that already are int32 (slots, det_index) or uint8 / bool (new) are read in place,
+    other dtypes converted with one tensor op; host lists travel together in one pinned upload.  add and release are one kernel launch each,
+    ordered on torch's current stream; with all operands on the device no call synchronises."""
 
     def __init__(self, capacity, budget, E, ctx=None):
         capacity, budget, E = int(capacity), int(budget), int(E)
@@ -55,28 +47,36 @@ class GhostGallery:
         self.mv_avg, self.mv_seen = self._mv_avg[:capacity], self._mv_seen[:capacity]
 
     def _tables(self, what, k, **cols):
-        """The index / flag vectors of one call (each None, a host sequence or a device tensor, `k` entries) as device int64 tensors: the host
-        ones travel together, in one upload."""
+        """The index / flag vectors of one call (each None, a host sequence or a device tensor, `k` entries) as contiguous device tensors, int32 or
+        for `new` uint8 / bool: a device tensor of that kind is used as it is, the host ones travel together, in one upload."""
         out, host = {}, {}
         for name, v in cols.items():
             if v is None:
                 out[name] = None
                 continue
+            flag = name == "new"
             if not torch.is_tensor(v):
                 v = np.asarray(v).reshape(-1)
-                host[name] = v = (v != 0).astype(np.int32) if name == "new" else v.astype(np.int32)
+                host[name] = v = (v != 0).astype(np.uint8) if flag else v.astype(np.int32)
             if (v.numel() if torch.is_tensor(v) else len(v)) != k:
                 raise ValueError("%s: %d entries of `%s` for %d slots" % (what, v.numel() if torch.is_tensor(v) else len(v), name, k))
             if torch.is_tensor(v):
-                out[name] = v.to(self.dev).view(-1).long()
+                if flag and v.dtype not in _FLAG_DTYPES:
+                    v = v != 0
+                if not (v.device == self.dev and v.is_contiguous() and v.dtype in (_FLAG_DTYPES if flag else (torch.int32,))):
+                    v = v.to(device=self.dev, dtype=v.dtype if flag else torch.int32).contiguous()
+                out[name] = v
         if host and k:
-            up =small_to_dev(np.stack(list(host.values())), self.dev, torch.int32).view(len(host), k).long()
-            out.update({name: up[i] for i, name in enumerate(host)})
+            names = sorted(host, key=lambda name: name == "new")                 # the int32 columns first: each starts on a multiple of 4 bytes
+            up, lo = h2d_async(np.concatenate([host[name].view(np.uint8) for name in names]), self.dev), 0
+            for name in names:
+                out[name] = up[lo:lo + host[name].nbytes].view(torch.uint8 if name == "new" else torch.int32)
+                lo += host[name].nbytes
         return out
 
     def add(self, slots, feats, det_index=None, new=None):
         """Row det_index[i] (None: i) of `feats` [m,E] (host array, or device float32 tensor read in place: the ReID output) becomes the newest
-        sample of slot slots[i]; new[i] true starts a new track in that slot first (ring emptied, mv_avg forgotten)."""
+        sample of slot slots[i]; new[i] true starts a new track in that slot first (ring emptied, mv_avg forgotten).  One busca_store_ring_add."""
         slots, k = _slots_checked(slots, self.capacity, "GhostGallery.add")
         feats = to_dev(feats, self.dev, torch.float32)
         if feats.dim() != 2 or feats.shape[1] != self.E:
@@ -86,18 +86,19 @@ class GhostGallery:
         t = self._tables("GhostGallery.add", k, slots=slots, det_index=det_index, new=new)
         if k == 0:
             return
-        rows = feats[:k] if t["det_index"] is None else feats.index_select(0, t["det_index"])
-        _ring_append(self._gallery, self._count, self._newest, self._mv_seen, t["slots"], rows, None if t["new"] is None else t["new"] != 0)
+        _store_lib.check(_store_lib.load().busca_store_ring_add(
+            self._gallery.data_ptr(), self._count.data_ptr(), self._newest.data_ptr(), self._mv_seen.data_ptr(), self.capacity, self.budget, self.E,
+            t["slots"].data_ptr(), k, feats.data_ptr(), feats.shape[0], ptr(t["det_index"]), ptr(t["new"]), self.dev.index, stream_of(self.dev)))
 
     def release(self, slots):
-        """The tracks in `slots` are gone: count = 0 and mv_seen = 0, so the slot reads as empty and can be given to a new track."""
+        """The tracks in `slots` are gone: count = 0 and mv_seen = 0, so the slot reads as empty and can be given to a new track.  One
+        busca_store_release."""
         slots, k = _slots_checked(slots, self.capacity, "GhostGallery.release")
         if k == 0:
             return
         s = self._tables("GhostGallery.release", k, slots=slots)["slots"]
-        s = torch.where(s < 0, self.capacity, s)
-        self._count.index_fill_(0, s, 0)
-        self._mv_seen.index_fill_(0, s, 0)
+        _store_lib.check(_store_lib.load().busca_store_release(self._count.data_ptr(), self._mv_seen.data_ptr(), self.capacity, s.data_ptr(), k,
+                                                               self.dev.index, stream_of(self.dev)))
 
     def state(self, active, inactive=(), motion=None):
         """The `state` of ghost_round for the tracks in the slots `active` followed by those in `inactive`: the tables themselves (not copies - the

@@ -7,7 +7,7 @@ each name is defined in the module of its family and re-exported here as the sam
   appearance    cosine gallery cost, NearestNeighborDistanceMetric, StrongSORT's appearance round               (busca_appearance.h)
   ghost         GHOST's proxy distances, proxies, thresholds, cost rules and round                             (busca_ghost.h)
   ghost_motion  GHOST's linear motion model                                                                    (busca_ghost_motion.h)
-  ghost_gallery GHOST's feature rings and moving-average table, the state ghost_round reads                    (no header: device tensor ops)
+  ghost_gallery GHOST's feature rings and moving-average table, the state ghost_round reads                    (busca_store.h, libbusca_store.so)
   ecc           camera-motion estimation for ByteTrack (u8 frames) and GHOST (float32 frames)                  (busca_hip.h, busca_ecc.h)
   crops         image crops and the host classes of the device crop pool                                       (busca_hip.h)
 Host arrays or device tensors go in; every call says in its docstring what comes back and where it lives.  There is no CPU implementation.

@@ -6,7 +6,8 @@
 Synthetic ReID features (busca_amd.synth.normal, E = 512) already in HBM, as the extractor leaves them; 50 tracks x 60 detections and 150 x 150,
 budget 32, every ring full, two thirds of the tracks active, every track matched to one detection per frame.  Every figure is the p50 in microseconds
 of `reps` frames after 20 warm-up frames, host clock around a frame that ends in ghost_round's (or distance's) device->host copy, so it is
-synchronised; the two routes of a row alternate inside one loop.
+synchronised; the two routes of a row alternate inside one loop.  device_p10_us / device_p90_us (and host_*) are the 10th and 90th percentile of the
+same frames: the spread a difference between two builds has to exceed.
 
 GHOST, per proxy ('mv_avg' with num 0.9 / 0.5, 'mean' with num 3), one frame = the round of this frame, then the matched features join the galleries:
   device_us   GhostGallery.state -> ghost_round -> GhostGallery.add(slots, <the device features>, det_index): nothing but the slot tables goes up,
@@ -14,11 +15,14 @@ GHOST, per proxy ('mv_avg' with num 0.9 / 0.5, 'mean' with num 3), one frame = t
   host_us     what a user has today: the features downloaded, Track.past_feats as host lists (and the mv_avg dict in numpy), a [n,budget,E] gallery
               rebuilt from the lists and uploaded every frame, then ghost_round on it.  'mv_avg' has no device route without the table, so the host
               route computes the proxies in numpy and hands ghost_round one vector per track
-  add_launches   device kernels + copies one GhostGallery.add enqueues (torch.profiler, host slot tables)
+  add_launches / release_launches   device kernels + copies one GhostGallery.add / release enqueues (torch.profiler, host slot tables: the pinned
+                 upload of the tables is one of them)
+  round_launches the same count for one ghost_round of the row's proxy, state() included: the proxy's launches and the rest of the round
 StrongSORT EMA (opt.EMA_alpha 0.9), one frame = partial_fit of the matched features, then metric.distance against all detections:
   device_us   partial_fit(<device features>, ema_alpha=0.9)
   host_us     download of the features, the four lines of deep_sort/track.py:244-248 in numpy per track, partial_fit of the smoothed rows
               (budget 1: the newest row replaces the old one; partial_fit renormalises, which leaves a unit vector as it is up to rounding)
+  fit_launches   device kernels + copies of one partial_fit(ema_alpha=) (the gather ddet[sel], the table upload and the count upload are among them)
 """
 import json
 import os
@@ -39,6 +43,10 @@ def p50(v):
     return float(np.median(v) * 1e6)
 
 
+def spread(name, v):
+    return {name + "_p10_us": float(np.percentile(v, 10) * 1e6), name + "_p90_us": float(np.percentile(v, 90) * 1e6)}
+
+
 def alternate(a, b, reps):
     for _ in range(20):
         a(); b()
@@ -46,7 +54,7 @@ def alternate(a, b, reps):
     for _ in range(reps):
         t0 = time.perf_counter(); a(); t1 = time.perf_counter(); b(); t2 = time.perf_counter()
         ta.append(t1 - t0); tb.append(t2 - t1)
-    return p50(ta), p50(tb)
+    return p50(ta), p50(tb), dict(spread("device", ta), **spread("host", tb))
 
 
 def launches(fn):
@@ -116,9 +124,11 @@ def main():
 
             got, want = device(), host()
             assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and len(got[0]) == min(n, m), "the two routes disagree at %d x %d %s" % (n, m, proxy)
-            td, th = alternate(device, host, reps)
-            rows.append(dict(case="GHOST %dx%d budget %d %s" % (n, m, BUDGET, proxy), device_us=td, host_us=th,
-                             add_launches=launches(lambda: store.add(slots, ddet, det_index=match))))
+            td, th, sp = alternate(device, host, reps)
+            rows.append(dict(case="GHOST %dx%d budget %d %s" % (n, m, BUDGET, proxy), device_us=td, host_us=th, **sp,
+                             add_launches=launches(lambda: store.add(slots, ddet, det_index=match)),
+                             round_launches=launches(lambda: tracking.ghost_round(store.state(active, inactive), ddet, cfg=cfg, ctx=ctx)),
+                             release_launches=launches(lambda: store.release(inactive))))
             print(json.dumps(rows[-1]), flush=True)
 
         # ---- StrongSORT EMA ----------------------------------------------------------------------------------------------------------
@@ -145,8 +155,8 @@ def main():
 
         got, want = device_ema(), host_ema()
         assert np.abs(got - want).max() < 1e-6, "the two EMA routes disagree at %d x %d" % (n, m)
-        td, th = alternate(device_ema, host_ema, reps)
-        rows.append(dict(case="StrongSORT EMA %dx%d" % (n, m), device_us=td, host_us=th,
+        td, th, sp = alternate(device_ema, host_ema, reps)
+        rows.append(dict(case="StrongSORT EMA %dx%d" % (n, m), device_us=td, host_us=th, **sp,
                          fit_launches=launches(lambda: dmetric.partial_fit(ddet[sel], ids, ids, ema_alpha=alpha))))
         print(json.dumps(rows[-1]), flush=True)
     res = dict(tool="tools/ghost_store_bench.py", E=E, budget=BUDGET, reps=reps, unit="us, p50 per frame", device=torch.cuda.get_device_name(0),
