@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so, libbusca_track.so and libbusca_store.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so and libbusca_rounds.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -28,6 +28,11 @@ TRACK_HEADERS = ["busca_track.h", "busca_hip.h"]
 STORE_OUT = os.path.join(HERE, "libbusca_store.so")
 STORE_UNITS = [("busca_store", False)]
 STORE_HEADERS = ["busca_store.h"]
+# libbusca_rounds.so (include/busca_rounds.h): the context-free library of association rounds batched across sequences.  Handled as the two above; it
+# compiles the kernel includes of the track library (and kalman_store_kernel with them), so an edit there rebuilds both.
+ROUNDS_OUT = os.path.join(HERE, "libbusca_rounds.so")
+ROUNDS_UNITS = [("busca_rounds", False)]
+ROUNDS_HEADERS = ["busca_rounds.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -132,9 +137,10 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the three libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the four libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
     _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
+    _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

@@ -8,7 +8,8 @@
 //  kstore_round_cost_kernel : the cost matrix of one association round - kalman_boxes, pairwise(IOU_COST), kalman_gating, the gate and the blend of
 //      matching.fuse_motion in one pass.  A PW_TA x PW_TB (16 x 64) tile per 256-lane workgroup, as pairwise_kernel: lanes 0 .. 15 stage one track
 //      each in LDS (the four box values, the projected mean and the Cholesky factor: 25 doubles), all lanes stage the detections, then every lane
-//      produces four outputs of one column.  The factor is computed once per tile, not once per lane as kalman_gating_kernel does.
+//      produces four outputs of one column.  The factor is computed once per tile, not once per lane as kalman_gating_kernel does.  The tile body is
+//      the device function kstore_round_cost_tile, which rounds_kernel.hip.inc (libbusca_rounds.so) calls once per (problem, tile) of a batch.
 
 #define KSTORE_FUSE_MOTION 1        // BUSCA_TRACK_FUSE_MOTION
 #define KSTORE_ONLY_POSITION 2      // BUSCA_TRACK_ONLY_POSITION
@@ -70,15 +71,17 @@ __global__ void __launch_bounds__(256) kstore_boxes_kernel(KStore k, int tlbr, d
     for (int c = 0; c < 4; ++c) o[c] = b[c];
 }
 
-__global__ void __launch_bounds__(256) kstore_round_cost_kernel(KStore k, const double* __restrict__ det_tlbr, const double* __restrict__ det_xyah,
-                                                                const double* __restrict__ det_score, int m, int flags, double lambda,
-                                                                double* __restrict__ out, int* __restrict__ status) {
+// The tile (a0, b0) of one round's cost matrix: rows a0 .. a0 + PW_TA - 1 of the list k.slot[0 .. k.n), columns b0 .. b0 + PW_TB - 1 of the m
+// detections, written to out[i * ld + j].  All 256 lanes of the workgroup call it (it holds a barrier).  `status` [k.n] is written by the tiles of
+// column block 0 alone.  kstore_round_cost_kernel and rounds_cost_kernel (rounds_kernel.hip.inc) are this function behind two addressings.
+__device__ __forceinline__ void kstore_round_cost_tile(const KStore& k, const double* __restrict__ det_tlbr, const double* __restrict__ det_xyah,
+                                                       const double* __restrict__ det_score, int m, int flags, double lambda,
+                                                       double* __restrict__ out, size_t ld, int* __restrict__ status, int a0, int b0) {
 #pragma clang fp contract(off)
     __shared__ double sbox[PW_TA][4], smu[PW_TA][4], sL[PW_TA][4][4];
     __shared__ int sstate[PW_TA];                                  // 0 a good track, 1 S not positive definite, 2 skipped
     __shared__ double sb[PW_TB][4], sz[PW_TB][4];
     const int tid = threadIdx.x;
-    const int a0 = blockIdx.y * PW_TA, b0 = blockIdx.x * PW_TB;
     const bool motion = (flags & (KSTORE_FUSE_MOTION | KSTORE_GATE_ONLY)) != 0;
     const int only_position = (flags & KSTORE_ONLY_POSITION) ? 1 : 0;
     if (tid < PW_TA) {
@@ -101,7 +104,7 @@ __global__ void __launch_bounds__(256) kstore_round_cost_kernel(KStore k, const 
             }
         }
         sstate[tid] = state;
-        if (blockIdx.x == 0 && t < k.n && status != nullptr) status[t] = state == 1 ? 1 : 0;
+        if (b0 == 0 && t < k.n && status != nullptr) status[t] = state == 1 ? 1 : 0;
     }
     {
         const int r = b0 + tid / 4;
@@ -141,6 +144,12 @@ __global__ void __launch_bounds__(256) kstore_round_cost_kernel(KStore k, const 
                 if (flags & KSTORE_FUSE_MOTION) v = lambda * v + (1.0 - lambda) * g;
             }
         }
-        out[(size_t)i * m + j] = v;
+        out[(size_t)i * ld + j] = v;
     }
+}
+
+__global__ void __launch_bounds__(256) kstore_round_cost_kernel(KStore k, const double* __restrict__ det_tlbr, const double* __restrict__ det_xyah,
+                                                                const double* __restrict__ det_score, int m, int flags, double lambda,
+                                                                double* __restrict__ out, int* __restrict__ status) {
+    kstore_round_cost_tile(k, det_tlbr, det_xyah, det_score, m, flags, lambda, out, (size_t)m, status, blockIdx.y * PW_TA, blockIdx.x * PW_TB);
 }

@@ -1,5 +1,6 @@
 """ByteTrack's Kalman state resident on the device: the means and covariances of all tracks stay in two device tensors over `capacity` slots, and
-every step names the slots it serves.  Fronts include/busca_track.h (libbusca_track.so, bound by _track_lib); restates what kalman.py restates -
+every step names the slots it serves.  Fronts include/busca_track.h (libbusca_track.so, bound by _track_lib) and, for the rounds of several sequences
+at once, include/busca_rounds.h (libbusca_rounds.so, bound by _rounds_lib); restates what kalman.py restates -
 adapters/ByteTrack/yolox/tracker/kalman_filter.py, matching.py:132-186, byte_tracker.py:50-61,67,78,109,142-163 - without the objects: no state
 crosses PCIe in either direction, and the cost matrix of an association round is one launch."""
 import collections
@@ -7,15 +8,27 @@ import collections
 import numpy as np
 import torch
 
-from . import _track_lib, geometry
+from . import _rounds_lib, _track_lib, geometry
 from ._xfer import small_to_dev, stream_of
-from .assignment import _assign_dev, _empty_triple, _solved
+from .assignment import _assign_dev, _empty_triple, _solved, _triple
 from .ghost_motion import _slots_checked
 from .kalman import _measurements, _raise_flagged, _set_states
 from .track_boxes import _tlbrs
 
 # the detections of a call on the device: tlbr [m,4], xyah [m,4], score [m] or None - views of one uploaded table
 DeviceDetections = collections.namedtuple("DeviceDetections", "tlbr xyah score m")
+# one sequence's association round in a batch (cost_batch, round_batch): a host slot list and what round() takes beside it
+RoundProblem = collections.namedtuple("RoundProblem", "slots detections det_scores not_tracked", defaults=(None, None))
+
+
+assert (_rounds_lib.FUSE_MOTION, _rounds_lib.ONLY_POSITION, _rounds_lib.GATE_ONLY) == (_track_lib.FUSE_MOTION, _track_lib.ONLY_POSITION, _track_lib.GATE_ONLY)
+
+
+def _scores(det_scores, m):
+    sc = np.asarray(det_scores, dtype=np.float64).reshape(-1)
+    if len(sc) != m:
+        raise ValueError("KalmanStore: %d scores for %d detections" % (len(sc), m))
+    return sc
 
 
 def _small(x, dev, dtype):
@@ -33,6 +46,8 @@ class KalmanStore:
       boxes(slots)                   STrack.tlbr / tlwh
       cost(slots, dets, ...)         the cost matrix of one association round, one launch -> (device [n,m], device status [n])
       round(slots, dets, thresh)     predict, cost and the linear assignment -> (matches, u_track, u_detection); one small device->host copy
+      detections_batch / cost_batch / round_batch(problems, ...)   the same for the rounds of many sequences that share the store: a list of
+                                     RoundProblem, one launch per step and one copy back whatever its length (busca_rounds_cost)
       load / store(slots, stracks)   states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
     `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors, allocated at the first call that needs them; the slot behind
     the last is a spare no kernel writes (the kernels are told `capacity`), where load / store park the negative entries of a slot list.
@@ -40,7 +55,7 @@ class KalmanStore:
     entry is skipped.  A slot list given as a device tensor is not read back: it is the caller's to keep distinct, and entries outside the capacity
     are skipped by the kernels and touch no memory.  Detections: objects with `.tlwh` (and `.tlbr` for cost / round), a host [m,4] array or device
     tensor of (x, y, a, h) measurements where only those are needed, or what detections() returned.  Every call is asynchronous on torch's
-    current stream of the device, except that round(), load() of nothing and store() wait for their one copy."""
+    current stream of the device, except that round(), round_batch(), load() of nothing and store() wait for their one copy."""
 
     def __init__(self, capacity, device=None):
         capacity = int(capacity)
@@ -82,18 +97,43 @@ class KalmanStore:
         if m == 0:
             none = torch.empty(0, 4, dtype=torch.float64, device=self.dev)
             return DeviceDetections(none if boxes else None, none, None, 0)
-        parts = [xyah.reshape(-1)]
-        if boxes:
-            parts.append(_tlbrs(detections).reshape(-1))
-        if det_scores is not None:
-            sc = np.asarray(det_scores, dtype=np.float64).reshape(-1)
-            if len(sc) != m:
-                raise ValueError("KalmanStore: %d scores for %d detections" % (len(sc), m))
-            parts.append(sc)
+        return self._det_table(xyah, _tlbrs(detections) if boxes else None, None if det_scores is None else _scores(det_scores, m))
+
+    def _det_table(self, xyah, tlbr, scores):
+        """One float64 upload of m > 0 measurements, their boxes (or None) and scores (or None) -> DeviceDetections of its views."""
+        m = xyah.shape[0]
+        parts = [xyah.reshape(-1)] + ([] if tlbr is None else [tlbr.reshape(-1)]) + ([] if scores is None else [scores])
         table = small_to_dev(np.concatenate(parts), self.dev, torch.float64)
-        score_at = 8 * m if boxes else 4 * m
-        return DeviceDetections(table[4 * m:8 * m].view(m, 4) if boxes else None, table[:4 * m].view(m, 4),
-                                table[score_at:score_at + m] if det_scores is not None else None, m)
+        score_at = 4 * m if tlbr is None else 8 * m
+        return DeviceDetections(None if tlbr is None else table[4 * m:8 * m].view(m, 4), table[:4 * m].view(m, 4),
+                                None if scores is None else table[score_at:score_at + m], m)
+
+    def detections_batch(self, list_of_detections, list_of_scores=None, boxes=True):
+        """The detections of several sequences as ONE table in one upload -> (DeviceDetections of the concatenation, host int32 [B + 1] `begin`):
+        sequence k's detections are rows begin[k] .. begin[k + 1] - 1, so one later update / initiate of all sequences indexes the table with
+        det_index + begin[k].  Each entry is what detections() takes from the host; boxes are kept when every entry is a list of objects.
+        `list_of_scores`: None, or one score vector per sequence - given for all sequences or for none, ValueError otherwise."""
+        B = len(list_of_detections)
+        scores = None
+        if list_of_scores is not None:
+            if len(list_of_scores) != B:
+                raise ValueError("KalmanStore.detections_batch: %d score vectors for %d detection lists" % (len(list_of_scores), B))
+            given = [sc is not None for sc in list_of_scores]
+            if any(given) != all(given):
+                raise ValueError("KalmanStore.detections_batch: scores are given for all problems or for none (problem %d has none)" % given.index(False))
+            scores = list_of_scores if B and given[0] else None
+        xyah = [_measurements(d) for d in list_of_detections]
+        begin = np.zeros(B + 1, dtype=np.int32)
+        begin[1:] = np.cumsum([z.shape[0] for z in xyah])
+        m = int(begin[-1])
+        boxes = boxes and not any(isinstance(d, np.ndarray) for d in list_of_detections)
+        if scores is not None:
+            scores = np.concatenate([_scores(sc, z.shape[0]) for sc, z in zip(scores, xyah)])
+        if m == 0:
+            none = torch.empty(0, 4, dtype=torch.float64, device=self.dev)
+            return DeviceDetections(none if boxes else None, none, None, 0), begin
+        tlbr = np.concatenate([_tlbrs(d) for d in list_of_detections]) if boxes else None
+        return self._det_table(np.concatenate(xyah), tlbr, scores), begin
 
     def _pairs(self, slots, detections, det_index, what):
         slot, n = self._slots(slots, what)
@@ -164,18 +204,22 @@ class KalmanStore:
         slot, n = self._slots(slots, "cost")
         return self._cost(slot, n, self.detections(detections, det_scores), fuse_motion, only_position, lambda_, gate_only)
 
-    def _cost(self, slot, n, det, fuse_motion, only_position, lambda_, gate_only=False):
+    @staticmethod
+    def _flags(det, fuse_motion, only_position, gate_only):
+        """The flag word of busca_track_round_cost / busca_rounds_cost (one set of values: busca_rounds.h takes busca_track.h's)."""
         if fuse_motion and gate_only:
             raise ValueError("KalmanStore.cost: fuse_motion and gate_only exclude each other")
         if det.tlbr is None:
             raise ValueError("KalmanStore.cost: the detections carry no boxes (objects with .tlbr and .tlwh are needed)")
+        flags = (_track_lib.FUSE_MOTION if fuse_motion else 0) | (_track_lib.GATE_ONLY if gate_only else 0)
+        return flags | _track_lib.ONLY_POSITION if flags and only_position else flags
+
+    def _cost(self, slot, n, det, fuse_motion, only_position, lambda_, gate_only=False):
+        flags = self._flags(det, fuse_motion, only_position, gate_only)
         out = torch.empty(n, det.m, dtype=torch.float64, device=self.dev)
         if n == 0 or det.m == 0:
             return out, torch.zeros(n, dtype=torch.int32, device=self.dev)
         status = torch.empty(n, dtype=torch.int32, device=self.dev)
-        flags = (_track_lib.FUSE_MOTION if fuse_motion else 0) | (_track_lib.GATE_ONLY if gate_only else 0)
-        if flags and only_position:
-            flags |= _track_lib.ONLY_POSITION
         lib = self._state()
         _track_lib.check(lib.busca_track_round_cost(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, det.tlbr.data_ptr(),
                                                     det.xyah.data_ptr(), None if det.score is None else det.score.data_ptr(), det.m, flags, float(lambda_),
@@ -198,6 +242,109 @@ class KalmanStore:
         host = torch.cat([sol.view(-1), status]).cpu().numpy()
         _raise_flagged(host[n + det.m + 1:], "KalmanStore.round")
         return _solved(host[:n + det.m + 1].astype(np.int64), n, det.m, "KalmanStore.round")
+
+    # ---- the rounds of many sequences in one launch each (busca_rounds.h, libbusca_rounds.so)
+    def _batch_checked(self, problems, what, distinct):
+        """The host side of a batch, before anything is allocated -> (RoundProblems, the concatenated slot list int32 [n_total], its begin [B + 1],
+        the concatenated `not_tracked` flags uint8 [n_total] or None).  Each slot list is checked as round() checks it; `distinct`: and the entries
+        >= 0 across the whole batch, which one predict launch would race on otherwise."""
+        problems = [p if isinstance(p, RoundProblem) else RoundProblem(*p) for p in problems]
+        if len(problems) > _rounds_lib.MAX_BATCH:
+            raise ValueError("KalmanStore.%s: %d problems, one call takes %d" % (what, len(problems), _rounds_lib.MAX_BATCH))
+        lists = []
+        for k, p in enumerate(problems):
+            if torch.is_tensor(p.slots):
+                raise ValueError("KalmanStore.%s takes host slot lists (problem %d)" % (what, k))
+            lists.append(_slots_checked(p.slots, self.capacity, "KalmanStore.%s: problem %d" % (what, k))[0])
+        begin = np.zeros(len(problems) + 1, dtype=np.int32)
+        begin[1:] = np.cumsum([len(s) for s in lists])
+        slots = np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, dtype=np.int32)
+        if distinct and len(problems) > 1:
+            live = slots[slots >= 0]
+            if len(np.unique(live)) != len(live):
+                raise ValueError("KalmanStore.%s: with predict the slots >= 0 must be distinct across the whole batch" % what)
+        nt = None
+        if any(p.not_tracked is not None for p in problems):
+            nt = np.zeros(len(slots), dtype=np.uint8)
+            for k, p in enumerate(problems):
+                if p.not_tracked is not None:
+                    flags = np.asarray(p.not_tracked, dtype=np.bool_).reshape(-1)
+                    if len(flags) != len(lists[k]):
+                        raise ValueError("KalmanStore.%s: problem %d has %d `not_tracked` flags for %d slots" % (what, k, len(flags), len(lists[k])))
+                    nt[begin[k]:begin[k + 1]] = flags
+        return problems, slots, begin, nt
+
+    def _batch_upload(self, problems, slots, begin, nt):
+        """The two uploads of a batch: the detections (detections_batch) and ONE int32 table - the slot list, the problem rows of busca_rounds_cost,
+        the solver's dims, the status words (zero: a problem without detections has no tile to write them) and, packed four to a word, the
+        `not_tracked` flags -> (views of the table: slot, rows, dims, status, flags or None; DeviceDetections; host dims int32 [B,2])."""
+        det, dbegin = self.detections_batch([p.detections for p in problems], [p.det_scores for p in problems])
+        B, n_total = len(problems), len(slots)
+        sizes = [n_total, 4 * B, 2 * B, n_total, 0 if nt is None else (n_total + 3) // 4]
+        host = np.zeros(sum(sizes), dtype=np.int32)
+        host[:n_total] = slots
+        rows, dims = host[n_total:n_total + 4 * B].reshape(B, 4), host[n_total + 4 * B:n_total + 6 * B].reshape(B, 2)
+        rows[:, 0], rows[:, 2] = begin[:-1], dbegin[:-1]
+        rows[:, 1] = dims[:, 0] = begin[1:] - begin[:-1]
+        rows[:, 3] = dims[:, 1] = dbegin[1:] - dbegin[:-1]
+        if nt is not None:
+            host[n_total + 6 * B + n_total:].view(np.uint8)[:n_total] = nt
+        views = list(small_to_dev(host, self.dev, torch.int32).split(sizes))
+        views[4] = None if nt is None else views[4].view(torch.uint8)[:n_total]
+        return views, det, dims
+
+    def _batch_cost(self, views, det, dims, flags, lambda_):
+        """busca_rounds_cost of an uploaded batch -> device float64 [B, N, M] (nothing is launched when every problem is empty)."""
+        slot, rows, _, status, _ = views
+        B, N, M = len(dims), int(dims[:, 0].max()), int(dims[:, 1].max())
+        out = torch.empty(B, N, M, dtype=torch.float64, device=self.dev)
+        if N == 0 or M == 0:
+            return out
+        self._state()
+        _rounds_lib.check(_rounds_lib.load().busca_rounds_cost(
+            self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), slot.numel(), det.tlbr.data_ptr(), det.xyah.data_ptr(),
+            None if det.score is None else det.score.data_ptr(), det.m, rows.data_ptr(), B, N, M, flags, float(lambda_), out.data_ptr(),
+            status.data_ptr(), *self._where()))
+        return out
+
+    def cost_batch(self, problems, fuse_motion=False, only_position=False, lambda_=0.98, gate_only=False):
+        """cost() of every RoundProblem(slots, detections, det_scores) of a list in ONE launch, from the states as they are -> (device float64
+        [B, N, M]: problem k's matrix is [k, :n_k, :m_k], the rest of the slab is not written; host int32 [B,2] of (n_k, m_k); device int32 [n_total]
+        status words in the order of the concatenated slot lists).  N and M are the largest n_k and m_k.  Problems may share slots.  Two uploads:
+        one int32 table, one float64 table of the detections."""
+        problems, slots, begin, _ = self._batch_checked(problems, "cost_batch", False)
+        if not problems:
+            return torch.empty(0, 0, 0, dtype=torch.float64, device=self.dev), np.zeros((0, 2), dtype=np.int32), torch.empty(0, dtype=torch.int32, device=self.dev)
+        views, det, dims = self._batch_upload(problems, slots, begin, None)
+        return self._batch_cost(views, det, dims, self._flags(det, fuse_motion, only_position, gate_only), lambda_), dims, views[3]
+
+    def round_batch(self, problems, thresh, fuse_motion=False, only_position=False, lambda_=0.98, predict=True):
+        """round() of every RoundProblem(slots, detections, det_scores, not_tracked) of a list -> [(matches, u_track, u_detection)], each what
+        round() returns for that problem alone.  Three launches whatever the number of problems - predict on the concatenated slot lists (unless
+        `predict` is false), busca_rounds_cost, busca_linear_assignment over the batch - and ONE device->host copy of B * (N + M + 1) match words
+        and n_total status words.  The sequences share this store: with `predict` the slots >= 0 must be distinct across the batch (ValueError).
+        Raises LinAlgError naming the problem and its track where round() does, after the prediction of every listed track."""
+        problems, slots, begin, nt = self._batch_checked(problems, "round_batch", predict)
+        if not problems:
+            return []
+        views, det, dims = self._batch_upload(problems, slots, begin, nt if predict else None)
+        flags = self._flags(det, fuse_motion, only_position, False) if det.m else 0
+        if predict and len(slots):
+            lib = self._state()
+            _track_lib.check(lib.busca_track_kalman_predict(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, views[0].data_ptr(),
+                                                            None if views[4] is None else views[4].data_ptr(), len(slots), *self._where()))
+        B, N, M = len(dims), int(dims[:, 0].max()), int(dims[:, 1].max())
+        if not (dims[:, 0] * dims[:, 1]).any():
+            return [_empty_triple(int(n), int(m)) for n, m in dims]
+        cost = self._batch_cost(views, det, dims, flags, lambda_)
+        sol = _assign_dev(geometry.default_context(self.dev.index), cost, B, N, M, thresh, views[2])
+        host = torch.cat([sol.view(-1), views[3]]).cpu().numpy()
+        sol, status = host[:B * (N + M + 1)].reshape(B, N + M + 1).astype(np.int64), host[B * (N + M + 1):]
+        for k in range(B):
+            if dims[k, 0] and dims[k, 1]:
+                _raise_flagged(status[begin[k]:begin[k + 1]], "KalmanStore.round_batch: problem %d" % k)
+        return [_empty_triple(int(n), int(m)) if n == 0 or m == 0 else _triple(sol[k, :n], sol[k, N:N + m], sol[k, N + M], "KalmanStore.round_batch[%d]" % k)
+                for k, (n, m) in enumerate(dims)]
 
     # ---- objects in and out
     def _rows(self, slots, stracks, what):

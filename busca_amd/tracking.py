@@ -2,7 +2,8 @@
 each name is defined in the module of its family and re-exported here as the same object.
   track_boxes   sentinel boxes, centre / IoU distances, duplicate removal, coverage, the BUSCA recovery rule   (busca_hip.h)
   kalman        ByteTrack's Kalman filter, gating, the predicted cost of a round                               (busca_hip.h)
-  kalman_store  the same filter on state that stays on the device: slots, rounds without a state copy          (busca_track.h, libbusca_track.so)
+  kalman_store  the same filter on state that stays on the device: slots, rounds without a state copy          (busca_track.h, libbusca_track.so;
+                the rounds of many sequences in one launch: busca_rounds.h, libbusca_rounds.so)
   assignment    linear assignment, min-cost matching, the matching cascade, associate_round                    (busca_assign.h)
   appearance    cosine gallery cost, NearestNeighborDistanceMetric, StrongSORT's appearance round               (busca_appearance.h)
   ghost         GHOST's proxy distances, proxies, thresholds, cost rules and round                             (busca_ghost.h)
@@ -31,6 +32,6 @@ from .ghost_gallery import GhostGallery  # noqa: F401
 from .ghost_motion import GhostMotion, ghost_motion_check_config  # noqa: F401
 from .kalman import (CHI2INV95, TRACKED, fuse_motion, gate_cost_matrix, gating_distance, multi_initiate, multi_predict, multi_update,  # noqa: F401
                      predicted_cost, tlwh_to_xyah)
-from .kalman_store import KalmanStore  # noqa: F401
+from .kalman_store import KalmanStore, RoundProblem  # noqa: F401
 from .track_boxes import (center_distance, get_detection_coverage, iou_distance, is_reliable, missing_candidate_bbox, recover_with_busca,  # noqa: F401
                           remove_duplicate_stracks, warp_pos)

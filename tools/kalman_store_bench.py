@@ -20,6 +20,16 @@ Both routes see the same states and must return the same matches in the first fr
   *_launches  device kernels + copies one frame of each route enqueues (torch.profiler)
   cost_us / chain_us   the cost matrix of a fuse_motion round alone, on states and detections already on the device: busca_track_round_cost (one
               launch) against busca_kalman_boxes + busca_pairwise (with its zero-fill) + busca_kalman_gating + torch.where + the blend
+
+    python tools/kalman_store_bench.py --sequences 1 2 4 8 16 [out.json] [reps=200]
+
+S sequences in lock-step over ONE store of S x (n + m) slots, each with the frame above on a scene of its own; written to
+profiles/kalman_store_batch_bench.json.  The two routes run on two stores loaded alike, alternating inside one loop as above:
+  loop_us     the frame above once per sequence: 3 S KalmanStore.round, S update, S initiate
+  batch_us    KalmanStore.round_batch x 3 over the S sequences, ONE update and ONE initiate on the concatenated lists (detections_batch)
+Both must return the same matches and initiations in the first frame and leave the same states, bit for bit, after the last (asserted).
+  *_launches  as above; per_sequence_us = batch_us / S
+
 Nothing here is a pass / fail criterion: the figures are reported as they come out, whichever route wins."""
 import json
 import os
@@ -101,9 +111,104 @@ def scene(k, n, m):
     return z, dets, scores
 
 
+def sequence_frame(store, q):
+    """The frame of one sequence through KalmanStore.round -> (the (slot, detection) pairs it updated, the detections it initiated).  `q`: the
+    sequence's slots, spare_slots, dets / high / low, scores, n_pool, mh and not_tracked."""
+    mt, ut, ud = store.round(q.slots[:q.n_pool], q.high, 0.8, det_scores=q.scores[:q.mh], not_tracked=q.not_tracked)
+    pairs = [(q.slots[i], j) for i, j in mt]
+    left = np.asarray([i for i in ut if not q.not_tracked[i]], dtype=np.int64)
+    m2, _, _ = store.round(q.slots[left], q.low, 0.5, predict=False)
+    pairs += [(q.slots[left[i]], q.mh + j) for i, j in m2]
+    rest = [q.high[j] for j in ud]
+    m3, _, ud3 = store.round(q.slots[q.n_pool:], rest, 0.7, det_scores=q.scores[:q.mh][list(ud)], predict=False)
+    pairs += [(q.slots[q.n_pool + i], ud[j]) for i, j in m3]
+    det_all = store.detections(q.dets, boxes=False)
+    store.update([p[0] for p in pairs], det_all, [p[1] for p in pairs])
+    new = [ud[j] for j in ud3]
+    store.initiate(q.spare_slots[:len(new)], det_all, new)
+    return pairs, new
+
+
+def batch_frame(store, seqs):
+    """The same frame of every sequence of a list at once: three round_batch, one update, one initiate -> [(pairs, initiations)] per sequence."""
+    from busca_amd.tracking import RoundProblem
+    r1 = store.round_batch([RoundProblem(q.slots[:q.n_pool], q.high, q.scores[:q.mh], q.not_tracked) for q in seqs], 0.8)
+    pairs = [[(q.slots[i], j) for i, j in mt] for q, (mt, _, _) in zip(seqs, r1)]
+    left = [np.asarray([i for i in ut if not q.not_tracked[i]], dtype=np.int64) for q, (_, ut, _) in zip(seqs, r1)]
+    r2 = store.round_batch([RoundProblem(q.slots[lf], q.low) for q, lf in zip(seqs, left)], 0.5, predict=False)
+    r3 = store.round_batch([RoundProblem(q.slots[q.n_pool:], [q.high[j] for j in ud], q.scores[:q.mh][list(ud)]) for q, (_, _, ud) in zip(seqs, r1)], 0.7,
+                           predict=False)
+    new = []
+    for k, (q, lf) in enumerate(zip(seqs, left)):
+        ud = r1[k][2]
+        pairs[k] += [(q.slots[lf[i]], q.mh + j) for i, j in r2[k][0]]
+        pairs[k] += [(q.slots[q.n_pool + i], ud[j]) for i, j in r3[k][0]]
+        new.append([ud[j] for j in r3[k][2]])
+    det_all, begin = store.detections_batch([q.dets for q in seqs], boxes=False)
+    store.update([p[0] for ps in pairs for p in ps], det_all, [p[1] + begin[k] for k, ps in enumerate(pairs) for p in ps])
+    store.initiate(np.concatenate([q.spare_slots[:len(nw)] for q, nw in zip(seqs, new)]), det_all, [j + begin[k] for k, nw in enumerate(new) for j in nw])
+    return list(zip(pairs, new))
+
+
+def main_sequences(counts, out_path, reps):
+    """--sequences: S sequences in lock-step over one store, a loop of sequence_frame against batch_frame."""
+    import torch
+    from busca_amd import _lib, geometry, tracking
+    assert torch.cuda.is_available(), "kalman_store_bench needs a GPU"
+    ctx = geometry.default_context(0)
+    dev = torch.device("cuda", 0)
+    sync = torch.cuda.current_stream(dev).synchronize
+    rows = []
+    for k, (n, m) in enumerate(CASES):
+        for S in counts:
+            stores = [tracking.KalmanStore(S * (n + m)) for _ in range(2)]      # [0] the loop's, [1] the batch's: alike, so both routes see the same states
+            seqs = []
+            for s in range(S):
+                z, dets, scores = scene(k + 2 * s, n, m)                        # (seeds 800 + k + 2 s: a scene of its own per sequence)
+                n_pool, mh = 4 * n // 5, 2 * m // 3
+                not_tracked = np.arange(n_pool) % 10 == 9
+                mean0, cov0 = tracking.multi_initiate(z, ctx=ctx)
+                slots = s * (n + m) + np.argsort(np.argsort((np.arange(n) * 7919) % 10007))
+                for st in stores:
+                    st.load(slots, [Track(mean0[i], cov0[i], 1) for i in range(n)])
+                seqs.append(types.SimpleNamespace(slots=slots, spare_slots=s * (n + m) + n + np.arange(m), dets=dets, high=dets[:mh], low=dets[mh:], scores=scores,
+                                                  n_pool=n_pool, mh=mh, not_tracked=not_tracked))
+
+            def loop():
+                return [sequence_frame(stores[0], q) for q in seqs]
+
+            def batch():
+                return batch_frame(stores[1], seqs)
+
+            def plain(result):
+                return [(sorted((int(a), int(b)) for a, b in pairs), sorted(int(j) for j in new)) for pairs, new in result]
+            a, b = plain(loop()), plain(batch())
+            assert a == b, "the two routes disagree at %d x %d, %d sequences" % (n, m, S)
+            tl, tb, spread = alternate(loop, batch, reps, sync)
+            assert torch.equal(stores[0].mean, stores[1].mean) and torch.equal(stores[0].cov, stores[1].cov), "states differ after %d frames" % (reps + 21)
+            rows.append(dict(case="ByteTrack frame %dx%d" % (n, m), sequences=S, pairs_per_frame=sum(len(p) for p, _ in a), initiations_per_frame=sum(len(w) for _, w in a),
+                             loop_us=tl, batch_us=tb, loop_p10_p90=spread[0], batch_p10_p90=spread[1], per_sequence_us=tb / S,
+                             loop_launches=launches(loop), batch_launches=launches(batch)))
+            print(json.dumps(rows[-1]), flush=True)
+    res = dict(tool="tools/kalman_store_bench.py --sequences", reps=reps, unit="us, p50 per frame of all sequences", device=torch.cuda.get_device_name(0),
+               host_threads=torch.get_num_threads(), build=_lib.build_info(ctx.lib), rows=rows)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main():
     import torch
     from busca_amd import _lib, geometry, kalman, tracking
+    if "--sequences" in sys.argv:
+        at = sys.argv.index("--sequences")
+        counts = []
+        while at + 1 + len(counts) < len(sys.argv) and sys.argv[at + 1 + len(counts)].isdigit():
+            counts.append(int(sys.argv[at + 1 + len(counts)]))
+        rest = sys.argv[1:at] + sys.argv[at + 1 + len(counts):]
+        return main_sequences(counts or [1, 2, 4, 8, 16], rest[0] if rest else os.path.join(ROOT, "profiles", "kalman_store_batch_bench.json"),
+                              int(rest[1]) if len(rest) > 1 else 200)
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "kalman_store_bench.json")
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
     assert torch.cuda.is_available(), "kalman_store_bench needs a GPU"
@@ -125,19 +230,10 @@ def main():
         spare_slots = n + np.arange(m)
         first = {}
 
+        seq = types.SimpleNamespace(slots=slots, spare_slots=spare_slots, dets=dets, high=high, low=low, scores=scores, n_pool=n_pool, mh=mh, not_tracked=not_tracked)
+
         def store_frame():
-            mt, ut, ud = store.round(slots[:n_pool], high, 0.8, det_scores=scores[:mh], not_tracked=not_tracked)
-            pairs = [(slots[i], j) for i, j in mt]
-            left = np.asarray([i for i in ut if not not_tracked[i]], dtype=np.int64)
-            m2, _, _ = store.round(slots[left], low, 0.5, predict=False)
-            pairs += [(slots[left[i]], mh + j) for i, j in m2]
-            rest = [high[j] for j in ud]
-            m3, _, ud3 = store.round(slots[n_pool:], rest, 0.7, det_scores=scores[:mh][list(ud)], predict=False)
-            pairs += [(slots[n_pool + i], ud[j]) for i, j in m3]
-            det_all = store.detections(dets, boxes=False)
-            store.update([p[0] for p in pairs], det_all, [p[1] for p in pairs])
-            new = [ud[j] for j in ud3]
-            store.initiate(spare_slots[:len(new)], det_all, new)
+            pairs, new = sequence_frame(store, seq)
             if "store" not in first:
                 first["store"] = (sorted((int(np.nonzero(slots == s)[0][0]), int(j)) for s, j in pairs), sorted(int(j) for j in new))
 
