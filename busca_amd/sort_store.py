@@ -1,0 +1,280 @@
+"""StrongSORT's Kalman state resident on the device: the means and covariances of all tracks stay in two device tensors over `capacity` slots, and
+every step names the slots it serves.  Fronts include/busca_sort.h (libbusca_sort.so, bound by _sort_lib) and, for the two steps whose arithmetic is
+ByteTrack's (initiate, the box conversions), include/busca_track.h through a KalmanStore over the same tensors.  Restates Track.predict / update /
+camera_update (adapters/StrongSORT/deep_sort/track.py:202-250), gate_cost_matrix with min_cost_matching's clamp (linear_assignment.py:61,164-210)
+and the two stages of Tracker._match (tracker.py:211-248) without the objects.  deep_sort/kalman_filter.py and iou_matching.py are not in the
+reference tree: predict, the confidence-scaled update and iou_cost are restated from upstream StrongSORT (DESIGN K-SORT)."""
+import numpy as np
+import torch
+
+from . import _sort_lib, geometry
+from ._xfer import stream_of, to_dev
+from .appearance import INFTY_COST
+from .assignment import _assign_dev, _solved
+from .ghost_motion import _slots_checked
+from .kalman import _measurements, _raise_flagged
+from .kalman_store import KalmanStore, _small
+
+
+def _xyah(detections):
+    """The measurements of a call: a device tensor or an [m,4] array of (x, y, a, h) as it is, `.to_xyah()` of deep_sort Detections, tlwh_to_xyah(.tlwh)
+    of other objects."""
+    if torch.is_tensor(detections) or isinstance(detections, np.ndarray):
+        return detections
+    if len(detections) and hasattr(detections[0], "to_xyah"):
+        return np.asarray([d.to_xyah() for d in detections], dtype=np.float64).reshape(-1, 4)
+    return _measurements(detections)
+
+
+class SortStore:
+    """The Kalman state of up to `capacity` StrongSORT tracks on the device (busca_sort_*, busca_track_kalman_initiate / _boxes):
+      initiate(slots, dets, det_index)       KalmanFilter.initiate: Track.__init__'s state of a new track - also how a slot is reused
+      predict(slots)                         Track.predict in place
+      update(slots, dets, det_index, confidence)   the NSA Kalman update of Track.update in place -> device status words
+      camera_update(slots, matrix)           Track.camera_update with one 3 x 3 warp
+      boxes(slots, tlbr)                     Track.to_tlbr / to_tlwh
+      gate_cost(slots, cost, det_xyah, ...)  gate_cost_matrix, the MC blend and the clamp on a cost matrix, one launch -> (device [n,m], status [n])
+      iou_cost(slots, det_tlwh, stale, ...)  iou_matching.iou_cost and the clamp, one launch -> device [n,m]
+      appearance_round(metric, slots, ...)   the first stage of Tracker._match: appearance.appearance_round on resident state
+      iou_round(slots, det_tlwh, ...)        its IoU stage: iou_cost, the clamp and the linear assignment; one copy, of match vectors
+      load / store(slots, tracks)            states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
+    `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors in the layout of KalmanStore, allocated at the first call that
+    needs them; the slot behind the last is a spare no kernel writes.  Slot lists given as host lists or arrays are checked on the host - the entries
+    >= 0 distinct and below `capacity`, ValueError otherwise; a negative entry is skipped.  A slot list given as a device tensor is read in place: it
+    is the caller's to keep distinct, and entries outside the capacity are skipped by the kernels and touch no memory.  Detections: an [m,4] host
+    array or device tensor of (x, y, a, h) measurements, or objects with `.to_xyah()` or `.tlwh`.  Every call is asynchronous on torch's current
+    stream of the device, except that the two rounds and store() wait for their one copy."""
+
+    def __init__(self, capacity, device=None):
+        if int(capacity) < 0:
+            raise ValueError("SortStore(capacity=%d)" % int(capacity))
+        self._k = KalmanStore(capacity, device)
+        self.capacity, self.dev = self._k.capacity, self._k.dev
+        self._lib = None
+
+    # ---- plumbing
+    mean = property(lambda self: self._k.mean, lambda self, t: setattr(self._k, "mean", t))
+    cov = property(lambda self: self._k.cov, lambda self, t: setattr(self._k, "cov", t))
+
+    def _state(self):
+        self._k._state()
+        if self._lib is None:
+            self._lib = _sort_lib.load()
+        return self._lib
+
+    def _slots(self, slots, what):
+        """-> (device i32 [n], n); a host list is checked first, before anything is allocated."""
+        slot, n = _slots_checked(slots, self.capacity, "SortStore." + what)
+        return _small(slot, self.dev, torch.int32), n
+
+    def _where(self):
+        return self.dev.index, stream_of(self.dev)
+
+    def _f64(self, x, cols, what):
+        """A host array (pinned staging) or device tensor as a contiguous device float64 [k, cols] (cols = 0: [k])."""
+        if not torch.is_tensor(x):
+            x = np.asarray(x, dtype=np.float64)
+        if cols and (x.ndim != 2 or x.shape[1] != cols) and x.size:
+            raise ValueError("SortStore.%s takes [m,%d] values, not %s" % (what, cols, tuple(x.shape)))
+        t = _small(x, self.dev, torch.float64)
+        return t.view(-1, cols) if cols else t
+
+    # ---- the filter
+    def initiate(self, slots, detections, det_index=None):
+        """KalmanFilter.initiate of detection det_index[i] (None: i) into slot slots[i]: a new track, or a new tenant of an abandoned slot."""
+        slot, _ = _slots_checked(slots, self.capacity, "SortStore.initiate")
+        self._k.initiate(slot, _xyah(detections), det_index)
+
+    def predict(self, slots):
+        """Track.predict of the listed slots in place."""
+        slot, n = self._slots(slots, "predict")
+        if n == 0:
+            return
+        lib = self._state()
+        _sort_lib.check(lib.busca_sort_predict(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, *self._where()))
+
+    def update(self, slots, detections, det_index=None, confidence=None):
+        """KalmanFilter.update(mean, covariance, xyah, confidence) of slot slots[i] with detection j = det_index[i] (None: i), in place -> device
+        int32 [n] status words: 1 where the reference raises LinAlgError (that slot keeps its state), which is the caller's to read or not.
+        `confidence`: None (0 for all), one number, or one per DETECTION ([m] host array or device tensor) - detection.confidence."""
+        slot, n = self._slots(slots, "update")
+        z = self._f64(_xyah(detections), 4, "update")
+        m = z.shape[0]
+        idx = None
+        if det_index is not None:
+            idx = _small(det_index if torch.is_tensor(det_index) else np.asarray(det_index, dtype=np.int32), self.dev, torch.int32)
+            if idx.numel() != n:
+                raise ValueError("SortStore.update: %d detection indices for %d slots" % (idx.numel(), n))
+        elif n > m:
+            raise ValueError("SortStore.update: %d slots for %d detections" % (n, m))
+        conf = None
+        if confidence is not None:
+            if not torch.is_tensor(confidence) and np.ndim(confidence) == 0:
+                confidence = np.full(m, float(confidence))
+            conf = self._f64(confidence, 0, "update")
+            if conf.numel() != m:
+                raise ValueError("SortStore.update: %d confidences for %d detections" % (conf.numel(), m))
+        status = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if n == 0:
+            return status
+        lib = self._state()
+        _sort_lib.check(lib.busca_sort_update(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, z.data_ptr(),
+                                              None if idx is None else idx.data_ptr(), m, None if conf is None else conf.data_ptr(), status.data_ptr(),
+                                              *self._where()))
+        return status
+
+    def camera_update(self, slots, matrix):
+        """Track.camera_update of the listed slots with the 3 x 3 warp `matrix` (host array or device tensor; what Track.get_matrix returned)."""
+        if not torch.is_tensor(matrix):
+            matrix = np.asarray(matrix, dtype=np.float64)
+        if tuple(matrix.shape) != (3, 3):
+            raise ValueError("SortStore.camera_update takes a 3 x 3 matrix, not %s" % (tuple(matrix.shape),))
+        slot, n = self._slots(slots, "camera_update")
+        if n == 0:
+            return
+        mat = _small(matrix, self.dev, torch.float64)
+        lib = self._state()
+        _sort_lib.check(lib.busca_sort_camera_update(self.mean.data_ptr(), self.capacity, slot.data_ptr(), n, mat.data_ptr(), *self._where()))
+
+    def boxes(self, slots, tlbr=True):
+        """Track.to_tlbr (to_tlwh with tlbr=False) of the listed slots -> device float64 [n,4]; a skipped entry: a row of NaN."""
+        slot, _ = _slots_checked(slots, self.capacity, "SortStore.boxes")
+        return self._k.boxes(slot, tlbr)
+
+    # ---- association
+    def _gate(self, slot, n, cost, ld_cost, z, mc_lambda, gated_cost, max_distance, out):
+        """busca_sort_gate_cost of n > 0 listed slots and m > 0 measurements into `out` (which may be `cost`) -> device status words [n]."""
+        flags = (_sort_lib.MC if mc_lambda is not None else 0) | (_sort_lib.CLAMP if max_distance is not None else 0)
+        status = torch.empty(n, dtype=torch.int32, device=self.dev)
+        lib = self._state()
+        _sort_lib.check(lib.busca_sort_gate_cost(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, z.data_ptr(), z.shape[0],
+                                                 cost.data_ptr(), ld_cost, float(gated_cost), flags, 0.0 if mc_lambda is None else float(mc_lambda),
+                                                 0.0 if max_distance is None else float(max_distance), out.data_ptr(), status.data_ptr(),
+                                                 *self._where()))
+        return status
+
+    def gate_cost(self, slots, cost, det_xyah, mc_lambda=None, gated_cost=INFTY_COST, max_distance=None):
+        """gate_cost_matrix of the [n,m] matrix `cost` (host array or device tensor, which is left as it is) from the states as they are: `gated_cost`
+        where the squared Mahalanobis distance of det_xyah[j] from slots[i]'s projection exceeds 9.4877; with `mc_lambda` every entry then becomes
+        mc_lambda * value + (1 - mc_lambda) * distance; with `max_distance` a value above it becomes max_distance + 1e-5 -> (device float64 [n,m],
+        device int32 [n] status words: 1 where the projected covariance is not positive definite, that row being NaN).  A skipped slot: a row of
+        `gated_cost`, clamped.  One launch."""
+        slot, n = self._slots(slots, "gate_cost")
+        z = self._f64(_xyah(det_xyah), 4, "gate_cost")
+        m = z.shape[0]
+        cost = to_dev(cost, self.dev, torch.float64)
+        if tuple(cost.shape) != (n, m):
+            raise ValueError("SortStore.gate_cost: a %s cost matrix for %d slots and %d detections" % (tuple(cost.shape), n, m))
+        out = torch.empty(n, m, dtype=torch.float64, device=self.dev)
+        if n == 0 or m == 0:
+            return out, torch.zeros(n, dtype=torch.int32, device=self.dev)
+        return out, self._gate(slot, n, cost, m, z, mc_lambda, gated_cost, max_distance, out)
+
+    def _stale(self, stale, n, what):
+        if stale is None:
+            return None
+        st = _small(stale if torch.is_tensor(stale) else np.asarray(stale, dtype=np.bool_).astype(np.uint8), self.dev, torch.uint8)
+        if st.numel() != n:
+            raise ValueError("SortStore.%s: %d `stale` flags for %d slots" % (what, st.numel(), n))
+        return st
+
+    def _iou(self, slot, n, st, boxes, max_distance):
+        out = torch.empty(n, boxes.shape[0], dtype=torch.float64, device=self.dev)
+        if n == 0 or boxes.shape[0] == 0:
+            return out
+        lib = self._state()
+        _sort_lib.check(lib.busca_sort_iou_cost(self.mean.data_ptr(), self.capacity, slot.data_ptr(), n, None if st is None else st.data_ptr(),
+                                                boxes.data_ptr(), boxes.shape[0], 0 if max_distance is None else _sort_lib.CLAMP,
+                                                0.0 if max_distance is None else float(max_distance), out.data_ptr(), *self._where()))
+        return out
+
+    def iou_cost(self, slots, det_tlwh, stale=None, max_distance=None):
+        """iou_matching.iou_cost of the listed tracks' to_tlwh() against the [m,4] boxes `det_tlwh` -> device float64 [n,m].  `stale`: [n] flags,
+        true where time_since_update > 1 - that row is INFTY_COST, as the row of a skipped slot is; `max_distance`: the clamp of min_cost_matching."""
+        slot, n = self._slots(slots, "iou_cost")
+        return self._iou(slot, n, self._stale(stale, n, "iou_cost"), self._f64(det_tlwh, 4, "iou_cost"), max_distance)
+
+    def appearance_round(self, metric, slots, track_ids, time_since_update, det_features, det_xyah, cascade_depth=None, mc_lambda=None):
+        """appearance.appearance_round on resident state: metric.distance of `det_features` [m,E] against the galleries of `track_ids` [n], then gate,
+        MC blend and the clamp at metric.matching_threshold in ONE busca_sort_gate_cost launch on that matrix, then busca_linear_assignment - with
+        `cascade_depth` once per level of the matching cascade over the tracks with time_since_update == 1 + level, without it (opt.woC) once.  The
+        same one device->host copy per level; no state and no matrix crosses.  `slots`, `track_ids`, `time_since_update`: one entry per track.
+        -> (matches [(row, detection)], unmatched rows, unmatched detections) with rows indexing `slots`, as appearance_round returns them for
+        track_indices = range(n)."""
+        slot, n = _slots_checked(slots, self.capacity, "SortStore.appearance_round")
+        track_ids = list(track_ids)
+        if len(track_ids) != n or (cascade_depth is not None and len(time_since_update) != n):
+            raise ValueError("SortStore.appearance_round: %d slots, %d track ids, %d time_since_update entries"
+                             % (n, len(track_ids), n if time_since_update is None else len(time_since_update)))
+        slot = _small(slot, self.dev, torch.int32)
+        z = self._f64(_xyah(det_xyah), 4, "appearance_round")
+        m = z.shape[0]
+        if n == 0 or m == 0:
+            return [], list(range(n)), list(range(m))
+        ctx = metric.ctx
+        feats = to_dev(det_features, self.dev, torch.float32)
+        if feats.shape[0] != m:
+            raise ValueError("SortStore.appearance_round: %d feature rows for %d detections" % (feats.shape[0], m))
+        cost = metric.distance(feats, track_ids, device=True)
+        kstatus = self._gate(slot, n, cost, m, z, mc_lambda, INFTY_COST, metric.matching_threshold, cost)
+        limit = metric.matching_threshold + 1e-5
+        if cascade_depth is None:
+            levels = [list(range(n))]
+        else:
+            levels = [[r for r in range(n) if time_since_update[r] == 1 + level] for level in range(cascade_depth)]
+        matches, cols, checked = [], list(range(m)), False
+        for rows in levels:
+            if len(cols) == 0:
+                break
+            if len(rows) == 0:
+                continue
+            if len(rows) == n and len(cols) == m:
+                sub = cost
+            else:
+                idx = torch.from_numpy(np.asarray(rows + cols, dtype=np.int64)).to(self.dev)     # one upload for both index vectors
+                sub = cost.index_select(0, idx[:len(rows)]).index_select(1, idx[len(rows):])
+            parts = [_assign_dev(ctx, sub.contiguous(), 1, len(rows), len(cols), limit).view(-1)]
+            if not checked:
+                parts.append(kstatus)
+            host = torch.cat(parts).cpu().numpy()                # one device->host copy: match vectors, solver status, Kalman status words
+            if not checked:
+                _raise_flagged(host[len(rows) + len(cols) + 1:], "SortStore.appearance_round")
+                checked = True
+            pairs, _, left = _solved(host, len(rows), len(cols), "SortStore.appearance_round")
+            matches += [(rows[r], cols[c]) for r, c in pairs]
+            cols = [cols[c] for c in left]
+        return matches, list(set(range(n)) - set(k for k, _ in matches)), cols
+
+    def iou_round(self, slots, det_tlwh, max_iou_distance, stale=None, detection_indices=None):
+        """The IoU stage of Tracker._match, min_cost_matching(iou_cost, max_iou_distance, ...) on resident state: the cost of the listed tracks
+        against det_tlwh[detection_indices] (None: all), clamped, and busca_linear_assignment with the limit max_iou_distance + 1e-5.  Two launches
+        and ONE device->host copy of n + m + 1 match words.  -> (matches [(row, detection)], unmatched rows, unmatched detections): rows index
+        `slots`, detections are entries of `detection_indices`."""
+        slot, n = self._slots(slots, "iou_round")
+        st = self._stale(stale, n, "iou_round")
+        if detection_indices is not None:
+            detection_indices = [int(j) for j in detection_indices]
+            if torch.is_tensor(det_tlwh):
+                det_tlwh = det_tlwh.to(self.dev).view(-1, 4)[torch.from_numpy(np.asarray(detection_indices, dtype=np.int64)).to(self.dev)]
+            else:
+                det_tlwh = np.asarray(det_tlwh, dtype=np.float64).reshape(-1, 4)[detection_indices]
+        boxes = self._f64(det_tlwh, 4, "iou_round")
+        m = boxes.shape[0]
+        dets = list(range(m)) if detection_indices is None else detection_indices
+        if n == 0 or m == 0:
+            return [], list(range(n)), dets
+        cost = self._iou(slot, n, st, boxes, max_iou_distance)
+        sol = _assign_dev(geometry.default_context(self.dev.index), cost, 1, n, m, max_iou_distance + 1e-5)
+        pairs, ua, ub = _solved(sol.cpu().numpy()[0], n, m, "SortStore.iou_round")
+        return [(int(r), dets[c]) for r, c in pairs], [int(r) for r in ua], [dets[c] for c in ub]
+
+    # ---- objects in and out
+    def load(self, slots, tracks):
+        """The states of objects with `.mean` [8] / `.covariance` [8,8] into their slots (one upload)."""
+        slot, _ = _slots_checked(slots, self.capacity, "SortStore.load")
+        self._k.load(slot, tracks)
+
+    def store(self, slots, tracks):
+        """The states of the listed slots into the objects' `.mean` / `.covariance` (one device->host copy)."""
+        slot, _ = _slots_checked(slots, self.capacity, "SortStore.store")
+        self._k.store(slot, tracks)
