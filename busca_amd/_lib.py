@@ -67,6 +67,15 @@ ASSIGN_SIGNATURES = {
 }
 ASSIGN_MAX = 2048              # BUSCA_ASSIGN_MAX
 
+# include/busca_assign_stages.h: the staged solver beside busca_linear_assignment.  Typed by load() after the tables of HEADERS, which stay the
+# headers of the one-call-one-problem interface as they were
+ASSIGN_STAGES_HEADER = "busca_assign_stages.h"
+ASSIGN_STAGES_API = {
+    "busca_assign_stages": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "busca_assign_stages_lds_bytes": (C.c_int64, [_i32, _i32, _i32]),
+}
+ASSIGN_STAGES_MAX = 128        # BUSCA_ASSIGN_STAGES_MAX
+
 # include/busca_appearance.h
 APPEARANCE_SIGNATURES = {
     "busca_appearance_cost": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
@@ -133,7 +142,7 @@ def load():
         # runtime (same device pointers, same streams).  Loading in the other order gives two runtimes.
         import torch  # noqa: F401
         lib = C.CDLL(os.environ.get("BUSCA_HIP_LIB", LIB_PATH))      # override: experiment builds of the same ABI
-        for table in HEADERS.values():
+        for table in list(HEADERS.values()) + [ASSIGN_STAGES_API]:
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)
                 fn.restype = res

@@ -1,11 +1,12 @@
-"""Linear assignment on the device and the association rounds that end in it.  Fronts busca_linear_assignment of include/busca_assign.h;
+"""Linear assignment on the device and the association rounds that end in it.  Fronts busca_linear_assignment of include/busca_assign.h and
+busca_assign_stages of include/busca_assign_stages.h (a chain of assignment problems in one launch);
 restates matching.linear_assignment (adapters/ByteTrack/yolox/tracker/matching.py:39-50, lap.lapjv) and min_cost_matching / matching_cascade
 (adapters/StrongSORT/deep_sort/linear_assignment.py:15-162).  A device cost matrix is never downloaded: only the match vectors cross."""
 import numpy as np
 import torch
 
 from . import _lib, geometry
-from ._xfer import stream_of, to_dev
+from ._xfer import h2d_async, small_to_dev, stream_of, to_dev
 from .kalman import _download_round, _predicted_cost_dev
 
 
@@ -79,6 +80,101 @@ def linear_assignment_batch(cost_matrices, thresh, ctx=None):
         res.append(_empty_triple(nk, mk) if nk == 0 or mk == 0 else
                    _triple(out[k, :nk], out[k, n:n + mk], out[k, n + m], "linear_assignment_batch[%d]" % k))
     return res
+
+
+def _stage_tables_dev(stages, first, again, dev):
+    """The three tables of busca_assign_stages as device pointers: the host ones go up in ONE pinned, asynchronous copy (the 16-byte stage records
+    first, so that every part stays aligned), device tensors are read in place.  -> (n_stages, stages ptr, first ptr, again ptr or None, the
+    tensors to keep alive behind the launch, the number of `first` entries)."""
+    keep, ptrs, host = [], {}, []
+    if torch.is_tensor(stages):
+        stages = stages.to(dev).contiguous()
+        nbytes = stages.numel() * stages.element_size()
+        if nbytes % 16:
+            raise ValueError("assign_stages: a device stage table holds 16-byte records {int32 plane, int32 0, float64 limit}, not %d bytes" % nbytes)
+        n_stages = nbytes // 16
+        keep.append(stages)
+        ptrs["stages"] = stages.data_ptr()
+    else:
+        recs = [(int(p), float(lim)) for p, lim in stages]
+        n_stages = len(recs)
+        table = np.zeros(n_stages, dtype=np.dtype([("plane", "<i4"), ("reserved", "<i4"), ("limit", "<f8")]))
+        table["plane"] = [p for p, _ in recs]
+        table["limit"] = [lim for _, lim in recs]
+        host.append(("stages", table.view(np.uint8).reshape(-1)))
+    if not 1 <= n_stages <= _lib.ASSIGN_STAGES_MAX:
+        raise ValueError("assign_stages: %d stages, 1 .. %d are supported" % (n_stages, _lib.ASSIGN_STAGES_MAX))
+    count = None
+    for name, x in (("first", first), ("again", again)):
+        if x is None:
+            ptrs[name] = None
+        elif torch.is_tensor(x):
+            x = x.to(device=dev, dtype=torch.int32).contiguous()
+            keep.append(x)
+            ptrs[name] = x.data_ptr()
+            count = x.numel() if name == "first" else count
+        else:
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.int32).reshape(-1))
+            host.append((name, x.view(np.uint8)))
+            count = x.size if name == "first" else count
+    if host:
+        up = h2d_async(np.concatenate([b for _, b in host]), dev)
+        keep.append(up)
+        off = 0
+        for name, b in host:
+            ptrs[name] = up.data_ptr() + off
+            off += b.size
+    return n_stages, ptrs["stages"], ptrs["first"], ptrs["again"], keep, count
+
+
+def _assign_stages_dev(ctx, cost, stages, first, again, dims, into=None):
+    """busca_assign_stages on a device [batch, planes, n, m] tensor -> flat device i32 tensor row_to_col [batch, n] | col_to_row [batch, m] |
+    row_stage [batch, n] | status [batch].  `into`: a contiguous device int32 tensor whose first batch (2 n + m + 1) words receive that instead (a
+    caller that sends more words home in the same copy)."""
+    batch, planes, n, m = cost.shape
+    if n > _lib.ASSIGN_MAX or m > _lib.ASSIGN_MAX:
+        raise ValueError("staged assignment of %d x %d: the device solver takes at most %d rows and columns" % (n, m, _lib.ASSIGN_MAX))
+    dev = cost.device
+    n_stages, p_stages, p_first, p_again, keep, count = _stage_tables_dev(stages, first, again, dev)
+    if count != batch * n:
+        raise ValueError("assign_stages: %d `first` entries for %d problems of %d rows" % (count, batch, n))
+    if again is not None and (again.numel() if torch.is_tensor(again) else np.size(again)) != batch * n:
+        raise ValueError("assign_stages: `again` has not %d entries" % (batch * n))
+    words = batch * (2 * n + m + 1)
+    out = torch.empty(words, dtype=torch.int32, device=dev) if into is None else into
+    if batch == 0 or n == 0 or m == 0:                           # nothing is launched: every row and column unmatched, status 0
+        out[:words - batch] = -1
+        out[words - batch:words] = 0
+        return out
+    base, o_c2r, o_stage, o_status = out.data_ptr(), 4 * batch * n, 4 * batch * (n + m), 4 * batch * (2 * n + m)
+    ctx.check(ctx.lib.busca_assign_stages(ctx.h, cost.data_ptr(), planes, batch, n, m, None if dims is None else dims.data_ptr(), p_stages, n_stages,
+                                          p_first, p_again, base, base + o_c2r, base + o_stage, base + o_status, stream_of(dev)))
+    del keep                                                     # the caching allocator keeps the blocks until the stream has passed the launch
+    return out
+
+
+def assign_stages(ctx, cost, stages, first, again=None, dims=None):
+    """busca_assign_stages (include/busca_assign_stages.h): a chain of assignment problems over one set of rows and columns in ONE launch - stage s
+    is linear_assignment, with that stage's limit, of the rows that take part in it against the columns the earlier stages left, ties included.
+      cost    device float64 [planes, n, m] or [batch, planes, n, m] (a host array is uploaded)
+      stages  a list of (plane, limit) pairs, or a device tensor of 16-byte records {int32 plane, int32 0, float64 limit}; 1 .. 128 stages
+      first   [n] / [batch, n] int32: the stage a row takes part in; `again`: the stage it takes part in once more if it is still unmatched then.
+              A value outside 0 .. len(stages) - 1, or an again <= first, means never
+      dims    None or int32 [batch, 2]: the valid corner of each problem, as in linear_assignment_batch
+    Host tables go up in one pinned, asynchronous copy; device tensors are read in place.  Nothing is downloaded: -> a flat device int32 tensor
+    row_to_col [batch, n] | col_to_row [batch, m] | row_stage [batch, n] | status [batch] (0 solved, 1 a loop bound ran out, 2 a plane index
+    outside the slab; with 1 or 2 that problem's outputs are all -1) - one copy for the caller."""
+    ctx, dev = geometry.ctx_dev(ctx)
+    cost = to_dev(cost, dev, torch.float64)
+    if cost.dim() == 3:
+        cost = cost.unsqueeze(0)
+    if cost.dim() != 4:
+        raise ValueError("assign_stages takes a [planes, n, m] or [batch, planes, n, m] cost tensor, not %s" % (tuple(cost.shape),))
+    if dims is not None:
+        dims = small_to_dev(dims if torch.is_tensor(dims) else np.asarray(dims, dtype=np.int32), dev, torch.int32)
+        if dims.numel() != 2 * cost.shape[0]:
+            raise ValueError("assign_stages: %d `dims` entries for %d problems" % (dims.numel(), cost.shape[0]))
+    return _assign_stages_dev(ctx, cost, stages, first, again, dims)
 
 
 def min_cost_matching(distance_metric, max_distance, tracks, detections, track_indices=None, detection_indices=None, ctx=None):

@@ -17,7 +17,7 @@ STAMP = OUT + ".flags"
 UNITS = [("busca_hip", True), ("busca_dt_f32", True), ("busca_dt_f16", True), ("busca_dt_x3", True), ("busca_dt_aux", False),
          ("busca_dtl_f32", True), ("busca_dtl_f16", True), ("busca_dtl_x3", True), ("busca_reid", True), ("busca_assign", False), ("busca_appear", False), ("busca_ghost", False), ("busca_ghost_motion", False)]
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-HEADERS = ["busca_hip.h", "busca_assign.h", "busca_appearance.h", "busca_ghost.h", "busca_ghost_motion.h", "busca_reid_bn.h", "busca_ecc.h"]
+HEADERS = ["busca_hip.h", "busca_assign.h", "busca_assign_stages.h", "busca_appearance.h", "busca_ghost.h", "busca_ghost_motion.h", "busca_reid_bn.h", "busca_ecc.h"]
 # libbusca_track.so (include/busca_track.h): the context-free library of device-resident tracker state.  Its own units, objects, stamp and staleness
 # check; the same flags, no MFMA in it.  It shares kernel includes with busca_hip (track_kernel, pairwise_kernel), so an edit there rebuilds both.
 TRACK_OUT = os.path.join(HERE, "libbusca_track.so")

@@ -4,7 +4,7 @@
 //   busca_dt_f32 / _f16 / _x3.hip   the fused Decision-Transformer kernel, one unit per arithmetic flavour   (+ busca_dt_aux.hip, see there)
 //   busca_dtl_f32 / _f16 / _x3.hip  the layer-wise Decision-Transformer path
 //   busca_reid.hip     the ReID extractor (every flavour) and its C-ABI
-//   busca_assign.hip   the linear-assignment solver and its C-ABI (include/busca_assign.h)
+//   busca_assign.hip   the linear-assignment solver, the staged solver beside it and their C-ABI (include/busca_assign.h, include/busca_assign_stages.h)
 //   busca_appear.hip   the cosine gallery-cost kernel and its C-ABI (include/busca_appearance.h)
 //   busca_ghost.hip    GHOST's proxy distances, proxies, thresholds and mask / blend pass and their C-ABI (include/busca_ghost.h)
 //   busca_ghost_motion.hip   GHOST's linear motion model - position rings, velocity step, camera warp - and its C-ABI (include/busca_ghost_motion.h)
@@ -74,8 +74,9 @@ struct BuscaOptions {
     int dt_exact_f32 = 0;     // 1 = a context loaded with BUSCA_PREC_F16X3 runs its forwards in exact float32 (the f32 fragment packing kept beside the split one):
                               // how the host re-runs a step whose x3 forward reported a clipped operand ("dt_status" 2)
     int crop_band = 1;        // BUSCA_CROP_BAND: 1 = crops through the LDS-staged band kernel (crop_band_kernel), 0 = one thread per output pixel (A/B, tests)
-    int assign_stage = -1;    // BUSCA_ASSIGN_STAGE: -1 = busca_linear_assignment stages the cost matrix in LDS when it fits beside the solver's state, 0 = never (A/B, tests)
-    int last_assign_staged = 0;   // read-only: 1 = the last busca_linear_assignment launch staged its cost matrices in LDS
+    int assign_stage = -1;    // BUSCA_ASSIGN_STAGE: -1 = busca_linear_assignment stages the cost matrix in LDS when it fits beside the solver's state, 0 = never (A/B, tests);
+                              // busca_assign_stages: likewise for the member rows of a stage
+    int last_assign_staged = 0;   // read-only: 1 = the last busca_linear_assignment / busca_assign_stages launch staged its costs in LDS
     int last_dt_grid = 0, last_dt_ntrk = 0, last_dt_split = 0;    // read-only: workgroups / tracks per workgroup / token-split tracks of the last fused launch
     int last_dt_unique = 0;   // read-only: 1 = the one-workgroup-per-track kernel of the last fused launch ran on the unique token rows (dt_fused_unique_kernel)
     int last_dt_prune = 0;    // read-only: 1 = the one-workgroup-per-track kernel of the last fused launch ran its last layer pruned

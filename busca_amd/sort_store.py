@@ -7,10 +7,10 @@ reference tree: predict, the confidence-scaled update and iou_cost are restated 
 import numpy as np
 import torch
 
-from . import _sort_lib, geometry
+from . import _lib, _sort_lib, geometry
 from ._xfer import stream_of, to_dev
 from .appearance import INFTY_COST
-from .assignment import _assign_dev, _solved
+from .assignment import _assign_dev, _assign_stages_dev, _solved
 from .ghost_motion import _slots_checked
 from .kalman import _measurements, _raise_flagged
 from .kalman_store import KalmanStore, _small
@@ -26,6 +26,24 @@ def _xyah(detections):
     return _measurements(detections)
 
 
+def _match_stage_tables(time_since_update, confirmed, cascade_depth):
+    """Tracker._match (adapters/StrongSORT/deep_sort/tracker.py:226-248) as the row tables of a staged assignment -> (first, again), int32 [n].
+    Stages 0 .. depth - 1 are the levels of matching_cascade (level l holds the confirmed tracks with time_since_update == 1 + l), stage `depth` is
+    the IoU stage: the unconfirmed tracks, and again the confirmed tracks with time_since_update == 1 that the cascade left unmatched.  A confirmed
+    track older than the cascade is deep takes part in nothing (-1).  cascade_depth=None (opt.woC): every confirmed track in stage 0, IoU stage 1."""
+    tsu = np.asarray(time_since_update, dtype=np.int64).reshape(-1)
+    conf = np.asarray(confirmed, dtype=bool).reshape(-1)
+    if len(tsu) != len(conf):
+        raise ValueError("_match_stage_tables: %d time_since_update entries, %d confirmed flags" % (len(tsu), len(conf)))
+    depth = 1 if cascade_depth is None else int(cascade_depth)
+    if not 0 <= depth < _lib.ASSIGN_STAGES_MAX:
+        raise ValueError("a cascade of depth %d: the staged solver takes %d stages, the IoU stage among them" % (depth, _lib.ASSIGN_STAGES_MAX))
+    level = np.zeros(len(tsu), dtype=np.int64) if cascade_depth is None else tsu - 1
+    first = np.where(conf, np.where((level >= 0) & (level < depth), level, -1), depth)
+    again = np.where(conf & (tsu == 1), depth, -1)
+    return first.astype(np.int32), again.astype(np.int32)
+
+
 class SortStore:
     """The Kalman state of up to `capacity` StrongSORT tracks on the device (busca_sort_*, busca_track_kalman_initiate / _boxes):
       initiate(slots, dets, det_index)       KalmanFilter.initiate: Track.__init__'s state of a new track - also how a slot is reused
@@ -37,13 +55,14 @@ class SortStore:
       iou_cost(slots, det_tlwh, stale, ...)  iou_matching.iou_cost and the clamp, one launch -> device [n,m]
       appearance_round(metric, slots, ...)   the first stage of Tracker._match: appearance.appearance_round on resident state
       iou_round(slots, det_tlwh, ...)        its IoU stage: iou_cost, the clamp and the linear assignment; one copy, of match vectors
+      match(metric, slots, ...)              the whole of Tracker._match - cascade, IoU stage, merge - as one staged assignment; ONE copy whatever the depth
       load / store(slots, tracks)            states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
     `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors in the layout of KalmanStore, allocated at the first call that
     needs them; the slot behind the last is a spare no kernel writes.  Slot lists given as host lists or arrays are checked on the host - the entries
     >= 0 distinct and below `capacity`, ValueError otherwise; a negative entry is skipped.  A slot list given as a device tensor is read in place: it
     is the caller's to keep distinct, and entries outside the capacity are skipped by the kernels and touch no memory.  Detections: an [m,4] host
     array or device tensor of (x, y, a, h) measurements, or objects with `.to_xyah()` or `.tlwh`.  Every call is asynchronous on torch's current
-    stream of the device, except that the two rounds and store() wait for their one copy."""
+    stream of the device, except that the rounds, match() and store() wait for their one copy."""
 
     def __init__(self, capacity, device=None):
         if int(capacity) < 0:
@@ -142,10 +161,12 @@ class SortStore:
         return self._k.boxes(slot, tlbr)
 
     # ---- association
-    def _gate(self, slot, n, cost, ld_cost, z, mc_lambda, gated_cost, max_distance, out):
-        """busca_sort_gate_cost of n > 0 listed slots and m > 0 measurements into `out` (which may be `cost`) -> device status words [n]."""
+    def _gate(self, slot, n, cost, ld_cost, z, mc_lambda, gated_cost, max_distance, out, status=None):
+        """busca_sort_gate_cost of n > 0 listed slots and m > 0 measurements into `out` (which may be `cost`) -> device status words [n] (`status`
+        if given: a contiguous int32 [n] view the words are written into)."""
         flags = (_sort_lib.MC if mc_lambda is not None else 0) | (_sort_lib.CLAMP if max_distance is not None else 0)
-        status = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=self.dev)
         lib = self._state()
         _sort_lib.check(lib.busca_sort_gate_cost(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, slot.data_ptr(), n, z.data_ptr(), z.shape[0],
                                                  cost.data_ptr(), ld_cost, float(gated_cost), flags, 0.0 if mc_lambda is None else float(mc_lambda),
@@ -178,8 +199,9 @@ class SortStore:
             raise ValueError("SortStore.%s: %d `stale` flags for %d slots" % (what, st.numel(), n))
         return st
 
-    def _iou(self, slot, n, st, boxes, max_distance):
-        out = torch.empty(n, boxes.shape[0], dtype=torch.float64, device=self.dev)
+    def _iou(self, slot, n, st, boxes, max_distance, out=None):
+        if out is None:
+            out = torch.empty(n, boxes.shape[0], dtype=torch.float64, device=self.dev)
         if n == 0 or boxes.shape[0] == 0:
             return out
         lib = self._state()
@@ -267,6 +289,55 @@ class SortStore:
         sol = _assign_dev(geometry.default_context(self.dev.index), cost, 1, n, m, max_iou_distance + 1e-5)
         pairs, ua, ub = _solved(sol.cpu().numpy()[0], n, m, "SortStore.iou_round")
         return [(int(r), dets[c]) for r, c in pairs], [int(r) for r in ua], [dets[c] for c in ub]
+
+    def match(self, metric, slots, track_ids, time_since_update, confirmed, det_features, det_xyah, det_tlwh, max_iou_distance, cascade_depth=None,
+              mc_lambda=None):
+        """Tracker._match (adapters/StrongSORT/deep_sort/tracker.py:214-252) on resident state as ONE staged assignment: metric.distance over all
+        n tracks, busca_sort_gate_cost into plane 0 and busca_sort_iou_cost into plane 1 of one [2, n, m] slab, the stage tables of
+        _match_stage_tables in one pinned upload, busca_assign_stages, and ONE device->host copy of the match vectors with the Kalman status words
+        of the gate behind them - whatever the depth of the cascade; no tensor op and no upload per level.  `slots`, `track_ids`,
+        `time_since_update`, `confirmed` (Track.is_confirmed()): one entry per track; `det_features` [m,E], `det_xyah` and `det_tlwh` [m,4]: one
+        row per detection.  `cascade_depth`: self.max_age, or None for opt.woC.  Raises LinAlgError where appearance_round on the confirmed tracks
+        raises it.  -> (matches [(row, detection)] of the cascade and of the IoU stage in stage order, unmatched rows, unmatched detections); rows
+        index `slots`.  appearance_round + iou_round, composed as _match composes them, give the same answer with a copy per populated level."""
+        slot, n = _slots_checked(slots, self.capacity, "SortStore.match")
+        track_ids = list(track_ids)
+        z, boxes = _xyah(det_xyah), det_tlwh
+        boxes = boxes if torch.is_tensor(boxes) else np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+        m = len(z)
+        if not (len(track_ids) == len(time_since_update) == len(confirmed) == n):
+            raise ValueError("SortStore.match: %d slots, %d track ids, %d time_since_update entries, %d confirmed flags"
+                             % (n, len(track_ids), len(time_since_update), len(confirmed)))
+        if len(det_features) != m or len(boxes) != m:
+            raise ValueError("SortStore.match: %d feature rows and %d tlwh boxes for %d detections" % (len(det_features), len(boxes), m))
+        first, again = _match_stage_tables(time_since_update, confirmed, cascade_depth)
+        if n == 0 or m == 0:
+            return [], list(range(n)), list(range(m))
+        depth = 1 if cascade_depth is None else int(cascade_depth)
+        stale = np.asarray(time_since_update).reshape(-1) > 1                  # iou_cost: the row of a track not updated in the last frame is INFTY_COST
+        slot = _small(slot, self.dev, torch.int32)
+        z = self._f64(z, 4, "match")
+        boxes = self._f64(boxes, 4, "match")
+        st = self._stale(stale, n, "match")
+        ctx = metric.ctx
+        feats = to_dev(det_features, self.dev, torch.float32)
+        cost = metric.distance(feats, track_ids, device=True)                  # a track without a gallery: a row of +inf, which no stage reads
+        slab = torch.empty(1, 2, n, m, dtype=torch.float64, device=self.dev)
+        words = 2 * n + m + 1
+        out = torch.empty(words + n, dtype=torch.int32, device=self.dev)       # the solver's words | the gate's status words: one copy
+        self._gate(slot, n, cost, m, z, mc_lambda, INFTY_COST, metric.matching_threshold, slab[0, 0], out[words:])
+        self._iou(slot, n, st, boxes, max_iou_distance, slab[0, 1])
+        stages = [(0, metric.matching_threshold + 1e-5)] * depth + [(1, max_iou_distance + 1e-5)]
+        _assign_stages_dev(ctx, slab, stages, first, again, None, into=out)
+        host = out.cpu().numpy()                                               # the one device->host copy
+        conf = np.asarray(confirmed, dtype=bool).reshape(-1)
+        if (first[conf] >= 0).any():           # appearance_round gates the confirmed tracks and reads their status words at its first populated level
+            _raise_flagged(host[words:] * conf, "SortStore.match")
+        if host[words - 1] != 0:
+            raise _lib.BuscaError("SortStore.match: the solver ran out of its loop bounds (status %d) - is a cost -inf or a limit infinite?" % int(host[words - 1]))
+        r2c, c2r, stage = host[:n], host[n:n + m], host[n + m:2 * n + m]
+        rows = [int(r) for r in np.lexsort((np.arange(n), stage)) if r2c[r] >= 0]      # by stage, then by row: the order _match lists them in
+        return [(r, int(r2c[r])) for r in rows], [int(r) for r in np.nonzero(r2c < 0)[0]], [int(j) for j in np.nonzero(c2r < 0)[0]]
 
     # ---- objects in and out
     def load(self, slots, tracks):

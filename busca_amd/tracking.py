@@ -4,8 +4,9 @@ each name is defined in the module of its family and re-exported here as the sam
   kalman        ByteTrack's Kalman filter, gating, the predicted cost of a round                               (busca_hip.h)
   kalman_store  the same filter on state that stays on the device: slots, rounds without a state copy          (busca_track.h, libbusca_track.so;
                 the rounds of many sequences in one launch: busca_rounds.h, libbusca_rounds.so)
-  sort_store    StrongSORT's filter on state that stays on the device: NSA update, camera update, gated rounds (busca_sort.h, libbusca_sort.so)
-  assignment    linear assignment, min-cost matching, the matching cascade, associate_round                    (busca_assign.h)
+  sort_store    StrongSORT's filter on state that stays on the device: NSA update, camera update, gated rounds, (busca_sort.h, libbusca_sort.so)
+                Tracker._match as one staged assignment
+  assignment    linear assignment, min-cost matching, the matching cascade, associate_round, staged assignment (busca_assign.h, busca_assign_stages.h)
   appearance    cosine gallery cost, NearestNeighborDistanceMetric, StrongSORT's appearance round               (busca_appearance.h)
   ghost         GHOST's proxy distances, proxies, thresholds, cost rules and round                             (busca_ghost.h)
   ghost_motion  GHOST's linear motion model                                                                    (busca_ghost_motion.h)
@@ -22,7 +23,7 @@ import torch  # noqa: F401
 from . import geometry  # noqa: F401
 from .appearance import (INFTY_COST, NearestNeighborDistanceMetric, appearance_cost, appearance_round, embedding_distance,  # noqa: F401
                          fuse_iou, gate_cost_matrix_mc)
-from .assignment import associate_round, linear_assignment, linear_assignment_batch, matching_cascade, min_cost_matching  # noqa: F401
+from .assignment import assign_stages, associate_round, linear_assignment, linear_assignment_batch, matching_cascade, min_cost_matching  # noqa: F401
 from .crop_pool import Slot  # noqa: F401
 from .crops import DeviceBackedCrops, DeviceCrop, DeviceCrops, FrameHostCopy, get_bbox_crop, get_image_crops, normalize_crops  # noqa: F401
 from .ecc import (GhostCameraMotion, camera_motion_compensation, find_transform_ecc, find_transform_ecc_f32, ghost_ecc_check_config,  # noqa: F401
