@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so and libbusca_sort.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so and libbusca_frame.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -38,6 +38,12 @@ ROUNDS_HEADERS = ["busca_rounds.h", "busca_hip.h"]
 SORT_OUT = os.path.join(HERE, "libbusca_sort.so")
 SORT_UNITS = [("busca_sort", False)]
 SORT_HEADERS = ["busca_sort.h", "busca_hip.h"]
+# libbusca_frame.so (include/busca_frame.h): the context-free library of a ByteTrack frame on resident state - the cost slab of the three rounds and
+# the match vectors applied to the Kalman state.  Handled as the four above; it compiles the kernel includes of the track library under its own
+# frame_kernel, so an edit there rebuilds it too.
+FRAME_OUT = os.path.join(HERE, "libbusca_frame.so")
+FRAME_UNITS = [("busca_frame", False)]
+FRAME_HEADERS = ["busca_frame.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -142,11 +148,12 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the five libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the six libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
     _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
     _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
     _build_lib(SORT_OUT, SORT_UNITS, SORT_HEADERS, force, verbose)
+    _build_lib(FRAME_OUT, FRAME_UNITS, FRAME_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

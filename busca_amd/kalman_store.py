@@ -1,6 +1,7 @@
 """ByteTrack's Kalman state resident on the device: the means and covariances of all tracks stay in two device tensors over `capacity` slots, and
 every step names the slots it serves.  Fronts include/busca_track.h (libbusca_track.so, bound by _track_lib) and, for the rounds of several sequences
-at once, include/busca_rounds.h (libbusca_rounds.so, bound by _rounds_lib); restates what kalman.py restates -
+at once, include/busca_rounds.h (libbusca_rounds.so, bound by _rounds_lib), and for a whole frame as one chain include/busca_frame.h
+(libbusca_frame.so, bound by _frame_lib); restates what kalman.py restates -
 adapters/ByteTrack/yolox/tracker/kalman_filter.py, matching.py:132-186, byte_tracker.py:50-61,67,78,109,142-163 - without the objects: no state
 crosses PCIe in either direction, and the cost matrix of an association round is one launch."""
 import collections
@@ -8,9 +9,9 @@ import collections
 import numpy as np
 import torch
 
-from . import _rounds_lib, _track_lib, geometry
-from ._xfer import small_to_dev, stream_of
-from .assignment import _assign_dev, _empty_triple, _solved, _triple
+from . import _frame_lib, _lib, _rounds_lib, _track_lib, geometry
+from ._xfer import h2d_async, small_to_dev, stream_of
+from .assignment import _assign_dev, _assign_stages_dev, _empty_triple, _solved, _triple
 from .ghost_motion import _slots_checked
 from .kalman import _measurements, _raise_flagged, _set_states
 from .track_boxes import _tlbrs
@@ -19,6 +20,12 @@ from .track_boxes import _tlbrs
 DeviceDetections = collections.namedtuple("DeviceDetections", "tlbr xyah score m")
 # one sequence's association round in a batch (cost_batch, round_batch): a host slot list and what round() takes beside it
 RoundProblem = collections.namedtuple("RoundProblem", "slots detections det_scores not_tracked", defaults=(None, None))
+# what KalmanStore.frame returns: the matches of the three rounds as (row, detection) - rows index pool_slots (first, second) or unconfirmed_slots
+# (unconfirmed), detections the list as given, each list ascending by row -, the pool rows no round matched (those that are Tracked, then the lost
+# ones: byte_tracker.py:364), the unconfirmed rows left over, the tracks started as (detection, slot), the detections that would have started one but
+# found the store full, and the class of every detection (0 first round, 1 second round, 2 neither)
+ByteFrame = collections.namedtuple("ByteFrame", "first second unconfirmed unmatched_pool unmatched_unconfirmed new_tracks overflow det_class")
+FRAME_STAGES = 3               # first round, second round, unconfirmed round
 
 
 assert (_rounds_lib.FUSE_MOTION, _rounds_lib.ONLY_POSITION, _rounds_lib.GATE_ONLY) == (_track_lib.FUSE_MOTION, _track_lib.ONLY_POSITION, _track_lib.GATE_ONLY)
@@ -38,6 +45,43 @@ def _small(x, dev, dtype):
     return small_to_dev(x, dev, dtype)
 
 
+def _frame_classes(det_scores, track_thresh, low_thresh=0.1):
+    """The round of every detection by the comparisons of byte_tracker.py:244-249, made by numpy on the scores as given -> uint8 [m]: 0 where
+    score > track_thresh (first round), 1 where score > low_thresh and score < track_thresh (second round), 2 elsewhere - a score equal to
+    track_thresh, or not above low_thresh, belongs to neither round."""
+    scores = np.asarray(det_scores).reshape(-1)
+    remain = scores > track_thresh
+    second = np.logical_and(scores > low_thresh, scores < track_thresh)
+    cls = np.full(len(scores), _frame_lib.CLASS_NONE, dtype=np.uint8)
+    cls[second] = _frame_lib.CLASS_SECOND
+    cls[remain] = _frame_lib.CLASS_FIRST
+    return cls
+
+
+def _frame_row_tables(lost, n_pool, n_unconfirmed):
+    """The row tables of a frame's staged assignment -> (first, again) int32 [n_pool + n_unconfirmed], (lost) bool [n_pool].  Stage 0 is the first
+    round (every pool row), stage 1 the second (again the pool rows that are Tracked), stage 2 the round of the unconfirmed tracks."""
+    lost = np.asarray(lost, dtype=np.bool_).reshape(-1)
+    if len(lost) != n_pool:
+        raise ValueError("KalmanStore.frame: %d `lost` flags for %d pool slots" % (len(lost), n_pool))
+    first = np.concatenate([np.zeros(n_pool, dtype=np.int32), np.full(n_unconfirmed, 2, dtype=np.int32)])
+    again = np.concatenate([np.where(lost, -1, 1).astype(np.int32), np.full(n_unconfirmed, -1, dtype=np.int32)])
+    return first, again, lost
+
+
+def _frame_detections(detections):
+    """The detections of frame() on the host -> (measurements [m,4], boxes [m,4]).  Objects give tlwh_to_xyah(.tlwh) and .tlbr, as everywhere; a
+    host [m,4] array is taken as (x, y, a, h) measurements, exactly, and the boxes follow as STrack.tlbr derives them from a state."""
+    if torch.is_tensor(detections) or isinstance(detections, DeviceDetections):
+        raise ValueError("KalmanStore.frame takes detection objects with .tlwh and .tlbr, or a host [m,4] array of measurements")
+    xyah = _measurements(detections)
+    if not isinstance(detections, np.ndarray):
+        return xyah, _tlbrs(detections)
+    wh = np.stack([xyah[:, 2] * xyah[:, 3], xyah[:, 3]], 1)
+    tl = xyah[:, :2] - wh / 2
+    return xyah, np.concatenate([tl, wh + tl], 1)
+
+
 class KalmanStore:
     """The Kalman state of up to `capacity` tracks on the device (busca_track_kalman_*, busca_track_round_cost):
       initiate(slots, dets)          KalmanFilter.initiate: STrack.activate's state of a new track - also how a slot is reused
@@ -48,6 +92,8 @@ class KalmanStore:
       round(slots, dets, thresh)     predict, cost and the linear assignment -> (matches, u_track, u_detection); one small device->host copy
       detections_batch / cost_batch / round_batch(problems, ...)   the same for the rounds of many sequences that share the store: a list of
                                      RoundProblem, one launch per step and one copy back whatever its length (busca_rounds_cost)
+      frame(pool, lost, unconfirmed, dets, scores, ...)   a whole BYTETracker.update on the state: predict, the three rounds as one staged
+                                     assignment, update and initiation -> ByteFrame; four launches and one copy home whatever the track count
       load / store(slots, stracks)   states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
     `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors, allocated at the first call that needs them; the slot behind
     the last is a spare no kernel writes (the kernels are told `capacity`), where load / store park the negative entries of a slot list.
@@ -345,6 +391,117 @@ class KalmanStore:
                 _raise_flagged(status[begin[k]:begin[k + 1]], "KalmanStore.round_batch: problem %d" % k)
         return [_empty_triple(int(n), int(m)) if n == 0 or m == 0 else _triple(sol[k, :n], sol[k, N:N + m], sol[k, N + M], "KalmanStore.round_batch[%d]" % k)
                 for k, (n, m) in enumerate(dims)]
+
+    # ---- a whole frame as one chain (busca_frame.h, libbusca_frame.so; busca_assign_stages)
+    def _frame_checked(self, pool_slots, lost, unconfirmed_slots, free_slots, detections, det_scores, track_thresh, low_thresh):
+        """The host side of frame(), before anything is allocated -> (rows int32 [n]: pool then unconfirmed, n_pool, first, again, lost, free int32,
+        scores float64 [m], classes uint8 [m], measurements [m,4], boxes [m,4])."""
+        what = "KalmanStore.frame"
+        lists = []
+        for name, x in (("pool_slots", pool_slots), ("unconfirmed_slots", unconfirmed_slots), ("free_slots", free_slots)):
+            if torch.is_tensor(x):
+                raise ValueError("%s takes host slot lists (%s)" % (what, name))
+            lists.append(_slots_checked(x, self.capacity, "%s: %s" % (what, name))[0])
+        pool, unconfirmed, free = lists
+        if (free < 0).any():
+            raise ValueError("%s: a free slot is negative" % what)
+        rows = np.concatenate([pool, unconfirmed])
+        live = rows[rows >= 0]
+        if len(np.unique(live)) != len(live):
+            raise ValueError("%s: the slots of pool_slots and unconfirmed_slots together must be distinct" % what)
+        taken = np.intersect1d(live, free)
+        if len(taken):
+            raise ValueError("%s: free slot %d is also listed as a track's" % (what, int(taken[0])))
+        xyah, tlbr = _frame_detections(detections)
+        m = len(xyah)
+        scores = _scores(det_scores, m)
+        if len(rows) > _lib.ASSIGN_MAX or m > min(_lib.ASSIGN_MAX, _frame_lib.MAX_DETS):
+            raise ValueError("%s: %d tracks and %d detections, the device solver takes at most %d rows and columns" % (what, len(rows), m, _lib.ASSIGN_MAX))
+        first, again, lost = _frame_row_tables(lost, len(pool), len(unconfirmed))
+        return rows, len(pool), first, again, lost, free, scores, _frame_classes(det_scores, track_thresh, low_thresh), xyah, tlbr
+
+    def frame(self, pool_slots, lost, unconfirmed_slots, detections, det_scores, track_thresh, match_thresh, det_thresh, free_slots=(), mot20=False,
+              low_thresh=0.1, second_thresh=0.5, unconfirmed_thresh=0.7, apply=True):
+        """The Kalman side of one BYTETracker.update (adapters/ByteTrack/yolox/tracker/byte_tracker.py:244-249, 312-425) on resident state, as ONE
+        chain on the stream: STrack.multi_predict of the pool, the cost slab of the three rounds (busca_frame_cost), the three rounds as one staged
+        assignment (busca_assign_stages), and - unless `apply` is false - KalmanFilter.update of every matched track and KalmanFilter.initiate of
+        every new track into a free slot (busca_frame_apply) -> ByteFrame.  Four launches, two uploads and ONE device->host copy of 3 n + 2 m + 1
+        words whatever the track count; the host reads the matches after the filter has been enqueued, not before.
+          pool_slots         joint_stracks(tracked_stracks, lost_stracks), in that order;  lost[i]: the state of pool track i is not Tracked
+          unconfirmed_slots  the tracks with is_activated false: they are matched but, as in the reference, never predicted
+          detections         ALL detections of the frame: objects with .tlwh and .tlbr, or a host [m,4] array of (x, y, a, h) measurements, whose
+                             boxes then follow as STrack.tlbr derives them;  det_scores: their scores.  The rounds they belong to follow
+                             from the scores as in the reference (_frame_classes): > track_thresh first round, between low_thresh and track_thresh
+                             second round, the others - a score equal to track_thresh among them - none
+          match_thresh, second_thresh, unconfirmed_thresh   the limits of the three rounds;  mot20: no fuse_score in rounds one and three
+          det_thresh         an unmatched first-round detection starts a track unless its score is below this
+          free_slots         where new tracks go, in the order of their detections; disjoint from the listed tracks (ValueError otherwise).  A
+                             detection that finds none left is listed in ByteFrame.overflow and nothing is written for it
+        Rounds 1 and 3 read plane 0 of the slab, round 2 plane 1; a detection is kept out of a round by +inf in that round's plane, which to the
+        solver is a column that is not there.  Step 3b of the reference (the BUSCA round) matches tracks to their own Kalman candidates and takes no
+        detection away, so it commutes with the round of the unconfirmed tracks: it works on ByteFrame.unmatched_pool afterwards.
+        Raises LinAlgError where an update finds a projected covariance that is not positive definite (that track keeps its state, the others are
+        updated) and BuscaError on a solver status.  Without detections only the prediction happens and nothing is copied."""
+        rows, n_pool, first, again, lost, free, scores, cls, xyah, tlbr = self._frame_checked(pool_slots, lost, unconfirmed_slots, free_slots, detections,
+                                                                                  det_scores, track_thresh, low_thresh)
+        n, m, n_free = len(rows), len(xyah), len(free)
+        # one pinned upload of every small table: the 16-byte stage records first, then the int32 tables, then the `lost` bytes
+        stages = np.zeros(FRAME_STAGES, dtype=np.dtype([("plane", "<i4"), ("reserved", "<i4"), ("limit", "<f8")]))
+        stages["plane"] = [0, 1, 0]
+        stages["limit"] = [float(match_thresh), float(second_thresh), float(unconfirmed_thresh)]
+        ints = np.concatenate([rows, first, again, free]).astype(np.int32)
+        flags = np.zeros(-(-n_pool // 4) * 4, dtype=np.uint8)
+        flags[:n_pool] = lost
+        up = h2d_async(np.concatenate([stages.view(np.uint8).reshape(-1), ints.view(np.uint8), flags]), self.dev)
+        at = 16 * FRAME_STAGES
+        words = up[at:at + 4 * len(ints)].view(torch.int32)
+        d_slot, d_first, d_again, d_free = words[:n], words[n:2 * n], words[2 * n:3 * n], words[3 * n:]
+        d_lost = up[at + 4 * len(ints):]
+        lib = self._state()
+        where = self._where()
+        if n_pool:
+            _track_lib.check(lib.busca_track_kalman_predict(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), d_lost.data_ptr(),
+                                                            n_pool, *where))
+
+        def pool_left(r2c):                                                    # the Tracked rows no round matched, then the lost ones (:364)
+            return [i for i in range(n_pool) if r2c[i] < 0 and not lost[i]] + [i for i in range(n_pool) if r2c[i] < 0 and lost[i]]
+        if m == 0:
+            none = -np.ones(n, dtype=np.int64)
+            return ByteFrame([], [], [], pool_left(none), list(range(n - n_pool)), [], [], cls)
+        # one upload of the detection table: measurements, boxes, scores, and the class bytes behind them
+        tail = np.zeros(-(-m // 8) * 8, dtype=np.uint8)
+        tail[:m] = cls
+        table = small_to_dev(np.concatenate([xyah.reshape(-1), tlbr.reshape(-1), scores, tail.view(np.float64)]),
+                             self.dev, torch.float64)
+        d_xyah, d_tlbr, d_score, d_cls = table[:4 * m], table[4 * m:8 * m], table[8 * m:9 * m], table[9 * m:].view(torch.uint8)
+        solved = 2 * n + m + 1                                                 # row_to_col | col_to_row | row_stage | solver status
+        out = torch.empty(solved + n + m, dtype=torch.int32, device=self.dev)  # ... | update status [n] | new_slot [m]: one copy
+        slab = torch.empty(1, 2, n, m, dtype=torch.float64, device=self.dev)
+        flib = _frame_lib.load()
+        if n:
+            _frame_lib.check(flib.busca_frame_cost(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), n, d_tlbr.data_ptr(),
+                                                   None if mot20 else d_score.data_ptr(), d_cls.data_ptr(), m, slab.data_ptr(),
+                                                   out.data_ptr() + 4 * solved, *where))
+        _assign_stages_dev(geometry.default_context(self.dev.index), slab, up[:at], d_first, d_again, None, into=out)
+        if apply:
+            base = out.data_ptr()
+            _frame_lib.check(flib.busca_frame_apply(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr() if n else None, n,
+                                                    base if n else None, base + 4 * n, d_xyah.data_ptr(), d_score.data_ptr(), d_cls.data_ptr(), m,
+                                                    float(det_thresh), d_free.data_ptr() if n_free else None, n_free, base + 4 * (solved + n),
+                                                    base + 4 * solved if n else None, *where))
+        host = (out if apply else out[:solved + n]).cpu().numpy()              # the one device->host copy
+        if host[solved - 1] != 0:
+            raise _lib.BuscaError("KalmanStore.frame: the solver ran out of its loop bounds (status %d) - is a cost -inf or a limit infinite?"
+                                  % int(host[solved - 1]))
+        _raise_flagged(host[solved:solved + n], "KalmanStore.frame")
+        r2c, stage = host[:n], host[n + m:2 * n + m]
+        matched = [i for i in range(n) if r2c[i] >= 0]
+        new = host[solved + n:] if apply else np.full(m, -1, dtype=np.int32)
+        return ByteFrame([(i, int(r2c[i])) for i in matched if i < n_pool and stage[i] == 0],
+                         [(i, int(r2c[i])) for i in matched if i < n_pool and stage[i] == 1],
+                         [(i - n_pool, int(r2c[i])) for i in matched if i >= n_pool],
+                         pool_left(r2c), [i - n_pool for i in range(n_pool, n) if r2c[i] < 0],
+                         [(j, int(new[j])) for j in range(m) if new[j] >= 0], [j for j in range(m) if new[j] == -2], cls)
 
     # ---- objects in and out
     def _rows(self, slots, stracks, what):
