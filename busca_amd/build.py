@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so and libbusca_frame.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so and libbusca_sframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -44,6 +44,12 @@ SORT_HEADERS = ["busca_sort.h", "busca_hip.h"]
 FRAME_OUT = os.path.join(HERE, "libbusca_frame.so")
 FRAME_UNITS = [("busca_frame", False)]
 FRAME_HEADERS = ["busca_frame.h", "busca_hip.h"]
+# libbusca_sframe.so (include/busca_sframe.h): the context-free library of a StrongSORT frame on resident state - predict with the camera update, the
+# cost slab of Tracker._match and the match vectors applied to the Kalman state and the feature rows.  Handled as the five above; it compiles the kernel
+# includes of the sort and store libraries under its own sframe_kernel, so an edit there rebuilds it too.
+SFRAME_OUT = os.path.join(HERE, "libbusca_sframe.so")
+SFRAME_UNITS = [("busca_sframe", False)]
+SFRAME_HEADERS = ["busca_sframe.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -148,12 +154,13 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the six libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the seven libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
     _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
     _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
     _build_lib(SORT_OUT, SORT_UNITS, SORT_HEADERS, force, verbose)
     _build_lib(FRAME_OUT, FRAME_UNITS, FRAME_HEADERS, force, verbose)
+    _build_lib(SFRAME_OUT, SFRAME_UNITS, SFRAME_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

@@ -1,19 +1,45 @@
 """StrongSORT's Kalman state resident on the device: the means and covariances of all tracks stay in two device tensors over `capacity` slots, and
-every step names the slots it serves.  Fronts include/busca_sort.h (libbusca_sort.so, bound by _sort_lib) and, for the two steps whose arithmetic is
-ByteTrack's (initiate, the box conversions), include/busca_track.h through a KalmanStore over the same tensors.  Restates Track.predict / update /
+every step names the slots it serves.  Fronts include/busca_sort.h (libbusca_sort.so, bound by _sort_lib), for the two steps whose arithmetic is
+ByteTrack's (initiate, the box conversions) include/busca_track.h through a KalmanStore over the same tensors, and for a whole frame as one chain
+include/busca_sframe.h (libbusca_sframe.so, bound by _sframe_lib).  Restates Track.predict / update /
 camera_update (adapters/StrongSORT/deep_sort/track.py:202-250), gate_cost_matrix with min_cost_matching's clamp (linear_assignment.py:61,164-210)
 and the two stages of Tracker._match (tracker.py:211-248) without the objects.  deep_sort/kalman_filter.py and iou_matching.py are not in the
 reference tree: predict, the confidence-scaled update and iou_cost are restated from upstream StrongSORT (DESIGN K-SORT)."""
+import collections
+
 import numpy as np
 import torch
 
-from . import _lib, _sort_lib, geometry
-from ._xfer import stream_of, to_dev
+from . import _lib, _sframe_lib, _sort_lib, geometry
+from ._xfer import h2d_async, small_to_dev, stream_of, to_dev
 from .appearance import INFTY_COST
 from .assignment import _assign_dev, _assign_stages_dev, _solved
 from .ghost_motion import _slots_checked
 from .kalman import _measurements, _raise_flagged
 from .kalman_store import KalmanStore, _small
+
+
+# what SortStore.frame returns: the matches as (row, detection) in the order Tracker._match lists them (the cascade level by level, then the IoU
+# stage; rows index `slots`), the rows and the detections nothing matched, the tracks started as (detection, slot), and the detections that would have
+# started one but found the store full
+SortFrame = collections.namedtuple("SortFrame", "matches unmatched_tracks unmatched_detections new_tracks overflow")
+APPEAR_E_MIN, APPEAR_E_MAX = 16, 2048      # BUSCA_APPEAR_E_MIN / _MAX: the feature widths busca_appearance_cost takes (multiples of 16)
+
+assert (_sframe_lib.MC, _sframe_lib.CLAMP) == (_sort_lib.MC, _sort_lib.CLAMP)
+
+
+def _frame_boxes(det_tlwh):
+    """The detections of frame() on the host -> (tlwh [m,4], xyah [m,4]): a host [m,4] array of tlwh boxes or objects with `.tlwh`; the measurements
+    follow by the operations of Detection.to_xyah (deep_sort/detection.py: ret[:2] += ret[2:] / 2, ret[2] /= ret[3])."""
+    if torch.is_tensor(det_tlwh):
+        raise ValueError("SortStore.frame takes a host [m,4] array of tlwh boxes or detection objects with .tlwh")
+    if not isinstance(det_tlwh, np.ndarray) and len(det_tlwh) and hasattr(det_tlwh[0], "tlwh"):
+        det_tlwh = [d.tlwh for d in det_tlwh]
+    tlwh = np.array(det_tlwh, dtype=np.float64).reshape(-1, 4)
+    xyah = tlwh.copy()
+    xyah[:, :2] += xyah[:, 2:] / 2
+    xyah[:, 2] /= xyah[:, 3]
+    return tlwh, xyah
 
 
 def _xyah(detections):
@@ -56,19 +82,28 @@ class SortStore:
       appearance_round(metric, slots, ...)   the first stage of Tracker._match: appearance.appearance_round on resident state
       iou_round(slots, det_tlwh, ...)        its IoU stage: iou_cost, the clamp and the linear assignment; one copy, of match vectors
       match(metric, slots, ...)              the whole of Tracker._match - cascade, IoU stage, merge - as one staged assignment; ONE copy whatever the depth
+      frame(slots, ...)                      a whole frame on the state and the feature rows: predict, camera update, _match, update and initiation as
+                                             ONE chain -> SortFrame; needs `feature_dim`
+      features / load_features(slots, ...)   the feature rows of the listed slots, out and in
       load / store(slots, tracks)            states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
     `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors in the layout of KalmanStore, allocated at the first call that
     needs them; the slot behind the last is a spare no kernel writes.  Slot lists given as host lists or arrays are checked on the host - the entries
     >= 0 distinct and below `capacity`, ValueError otherwise; a negative entry is skipped.  A slot list given as a device tensor is read in place: it
     is the caller's to keep distinct, and entries outside the capacity are skipped by the kernels and touch no memory.  Detections: an [m,4] host
     array or device tensor of (x, y, a, h) measurements, or objects with `.to_xyah()` or `.tlwh`.  Every call is asynchronous on torch's current
-    stream of the device, except that the rounds, match() and store() wait for their one copy."""
+    stream of the device, except that the rounds, match(), frame() and store() wait for their one copy.
+    With `feature_dim` = E the store also keeps `feat`, float32 [capacity + 1, E]: one row per slot, the track's features[-1] of
+    deep_sort/track.py (the EMA-smoothed, normalised appearance feature), allocated with the state and written by frame()."""
 
-    def __init__(self, capacity, device=None):
+    def __init__(self, capacity, device=None, feature_dim=None):
         if int(capacity) < 0:
             raise ValueError("SortStore(capacity=%d)" % int(capacity))
+        if feature_dim is not None and int(feature_dim) < 1:
+            raise ValueError("SortStore(feature_dim=%d)" % int(feature_dim))
         self._k = KalmanStore(capacity, device)
         self.capacity, self.dev = self._k.capacity, self._k.dev
+        self.feature_dim = None if feature_dim is None else int(feature_dim)
+        self.feat = None
         self._lib = None
 
     # ---- plumbing
@@ -77,6 +112,8 @@ class SortStore:
 
     def _state(self):
         self._k._state()
+        if self.feature_dim is not None and self.feat is None:
+            self.feat = torch.zeros(self.capacity + 1, self.feature_dim, dtype=torch.float32, device=self.dev)
         if self._lib is None:
             self._lib = _sort_lib.load()
         return self._lib
@@ -338,6 +375,177 @@ class SortStore:
         r2c, c2r, stage = host[:n], host[n:n + m], host[n + m:2 * n + m]
         rows = [int(r) for r in np.lexsort((np.arange(n), stage)) if r2c[r] >= 0]      # by stage, then by row: the order _match lists them in
         return [(r, int(r2c[r])) for r in rows], [int(r) for r in np.nonzero(r2c < 0)[0]], [int(j) for j in np.nonzero(c2r < 0)[0]]
+
+    # ---- a whole frame as one chain (busca_sframe.h, libbusca_sframe.so; busca_appearance_cost, busca_assign_stages)
+    def _frame_checked(self, slots, time_since_update, confirmed, det_tlwh, det_confidence, det_features, ema_alpha, free_slots, cascade_depth,
+                       camera_matrix, predict):
+        """The host side of frame(), before anything is allocated -> (slot int32 [n], first, again, stale uint8 [n], free int32, tlwh [m,4],
+        xyah [m,4], confidences [m] or None, matrix [9] or None)."""
+        what = "SortStore.frame"
+        if self.feature_dim is None:
+            raise ValueError("%s needs the feature rows: SortStore(capacity, feature_dim=E)" % what)
+        if not APPEAR_E_MIN <= self.feature_dim <= APPEAR_E_MAX or self.feature_dim % 16:
+            raise ValueError("%s: feature_dim %d - busca_appearance_cost takes a multiple of 16 in %d .. %d" % (what, self.feature_dim, APPEAR_E_MIN, APPEAR_E_MAX))
+        if ema_alpha is None or ema_alpha != ema_alpha:
+            raise ValueError("%s needs ema_alpha (opt.EMA_alpha): the feature row is the EMA of deep_sort/track.py:244-248" % what)
+        lists = []
+        for name, x in (("slots", slots), ("free_slots", free_slots)):
+            if torch.is_tensor(x):
+                raise ValueError("%s takes host slot lists (%s)" % (what, name))
+            lists.append(_slots_checked(x, self.capacity, "%s: %s" % (what, name))[0])
+        slot, free = lists
+        n = len(slot)
+        if (free < 0).any():
+            raise ValueError("%s: a free slot is negative" % what)
+        taken = np.intersect1d(slot[slot >= 0], free)
+        if len(taken):
+            raise ValueError("%s: free slot %d is also listed as a track's" % (what, int(taken[0])))
+        if not (len(time_since_update) == len(confirmed) == n):
+            raise ValueError("%s: %d slots, %d time_since_update entries, %d confirmed flags" % (what, n, len(time_since_update), len(confirmed)))
+        tlwh, xyah = _frame_boxes(det_tlwh)
+        m = len(tlwh)
+        conf = None
+        if det_confidence is not None:
+            conf = np.asarray(det_confidence, dtype=np.float64).reshape(-1)
+            if len(conf) != m:
+                raise ValueError("%s: %d confidences for %d detections" % (what, len(conf), m))
+        shape = tuple(det_features.shape) if hasattr(det_features, "shape") else np.shape(det_features)
+        if m and (len(shape) != 2 or shape[0] != m or shape[1] != self.feature_dim):
+            raise ValueError("%s: %s features for %d detections of a store with feature_dim %d" % (what, shape, m, self.feature_dim))
+        if n > _lib.ASSIGN_MAX or m > min(_lib.ASSIGN_MAX, _sframe_lib.MAX_DETS):
+            raise ValueError("%s: %d tracks and %d detections, the device solver takes at most %d rows and columns" % (what, n, m, _lib.ASSIGN_MAX))
+        first, again = _match_stage_tables(time_since_update, confirmed, cascade_depth)
+        matrix = None
+        if camera_matrix is not None:
+            if not predict:
+                raise ValueError("%s: the camera update follows the prediction; with predict=False call camera_update() yourself" % what)
+            if torch.is_tensor(camera_matrix):
+                raise ValueError("%s takes a host 3 x 3 camera matrix" % what)
+            matrix = np.asarray(camera_matrix, dtype=np.float64)
+            if matrix.shape != (3, 3):
+                raise ValueError("%s takes a 3 x 3 camera matrix, not %s" % (what, matrix.shape))
+            matrix = matrix.reshape(-1)
+        stale = (np.asarray(time_since_update, dtype=np.int64).reshape(-1) > 1).astype(np.uint8)
+        return slot, first, again, stale, free, tlwh, xyah, conf, matrix
+
+    def frame(self, slots, time_since_update, confirmed, det_tlwh, det_confidence, det_features, max_iou_distance, matching_threshold, ema_alpha,
+              free_slots=(), cascade_depth=None, mc_lambda=None, camera_matrix=None, predict=True, apply=True):
+        """One Tracker.predict / camera_update / update (adapters/StrongSORT/deep_sort/tracker.py:74-126, 197-252) on resident state as ONE chain on
+        the stream: busca_sframe_advance (Track.predict and, with `camera_matrix`, Track.camera_update), busca_appearance_cost of `det_features`
+        against the feature rows of the listed slots, busca_sframe_cost (both planes of the slab of match(), each row only in the planes its stage
+        reads), busca_assign_stages with the stage list and row tables of match(), and - unless `apply` is false - busca_sframe_apply: Track.update of
+        every matched track (the EMA feature row, track.py:244-248, then the NSA Kalman update with the detection's confidence) and
+        Tracker._initiate_track of every unmatched detection into a free slot (KalmanFilter.initiate and its normalised feature, track.py:85-87)
+        -> SortFrame.  Two uploads, five launches and ONE device->host copy of 4 n + 2 m + 1 words whatever the depth of the cascade; the host reads
+        the matches after the filter has been enqueued, not before.
+          slots, time_since_update, confirmed   host lists, one entry per track in Tracker.tracks order; time_since_update as _match reads it, after
+                             Track.predict's increment (match()'s convention); confirmed: Track.is_confirmed()
+          det_tlwh           ALL detections of the frame: a host [m,4] array of tlwh boxes or objects with .tlwh; the measurements follow by the
+                             operations of Detection.to_xyah.  det_confidence: [m] or None (0 for all)
+          det_features       [m, feature_dim] float32; a device tensor is read in place
+          matching_threshold, max_iou_distance   metric.matching_threshold and Tracker.max_iou_distance; cascade_depth: Tracker.max_age, None: opt.woC;
+                             mc_lambda: opt.MC_lambda or None;  ema_alpha: opt.EMA_alpha
+          free_slots         where new tracks go, in the order of their detections; disjoint from the listed tracks (ValueError otherwise).  A
+                             detection that finds none left is listed in SortFrame.overflow and nothing is written for it
+          predict=False      the states are predicted (and warped) already
+        The feature rows are the tracks' own from birth, tentative life included, as the reference's Track keeps them; a listed slot whose row was
+        never written (all zero) has NaN appearance costs, which no stage admits.  The reference's BUSCA third round (tracker.py:129-189) matches
+        unmatched tracks to their own Kalman candidates and takes no detection, so it commutes with the initiation of new tracks: it works on
+        SortFrame.unmatched_tracks through update() afterwards.  Hits, track states and deletion stay on the host.
+        Raises LinAlgError where the gate of a row that takes part in the cascade, or an update, finds a projected covariance that is not positive
+        definite (that track keeps its Kalman state, its feature row is smoothed all the same, the other tracks are updated) and BuscaError on a
+        solver status.  Without detections only the advance happens and nothing is copied; without tracks every detection starts a track."""
+        slot, first, again, stale, free, tlwh, xyah, conf, matrix = self._frame_checked(
+            slots, time_since_update, confirmed, det_tlwh, det_confidence, det_features, ema_alpha, free_slots, cascade_depth, camera_matrix, predict)
+        n, m, n_free, E = len(slot), len(tlwh), len(free), self.feature_dim
+        depth = 1 if cascade_depth is None else int(cascade_depth)
+        # one pinned upload of every small table: the 16-byte stage records first, then the int32 tables, then the `stale` bytes
+        stages = np.zeros(depth + 1, dtype=np.dtype([("plane", "<i4"), ("reserved", "<i4"), ("limit", "<f8")]))
+        stages["plane"] = [0] * depth + [1]
+        stages["limit"] = [float(matching_threshold) + 1e-5] * depth + [float(max_iou_distance) + 1e-5]
+        ints = np.concatenate([slot, first, again, free]).astype(np.int32)
+        flags = np.zeros(-(-n // 4) * 4, dtype=np.uint8)
+        flags[:n] = stale
+        up = h2d_async(np.concatenate([stages.view(np.uint8).reshape(-1), ints.view(np.uint8), flags]), self.dev)
+        at = 16 * (depth + 1)
+        words = up[at:at + 4 * len(ints)].view(torch.int32)
+        d_slot, d_first, d_again, d_free = words[:n], words[n:2 * n], words[2 * n:3 * n], words[3 * n:]
+        d_stale = up[at + 4 * len(ints):]
+        # one float64 upload: measurements, boxes, confidences, the camera matrix
+        parts = ([xyah.reshape(-1), tlwh.reshape(-1)] if m else []) + ([conf] if m and conf is not None else []) + ([matrix] if matrix is not None else [])
+        table = small_to_dev(np.concatenate(parts), self.dev, torch.float64) if parts else None
+        d_xyah, d_tlwh = (table[:4 * m], table[4 * m:8 * m]) if m else (None, None)
+        d_conf = table[8 * m:9 * m] if m and conf is not None else None
+        d_matrix = table[table.numel() - 9:] if matrix is not None else None
+        self._state()
+        flib = _sframe_lib.load()
+        where = self._where()
+        if predict and n:
+            _sframe_lib.check(flib.busca_sframe_advance(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), n,
+                                                        _lib.ptr(d_matrix), *where))
+        if m == 0:
+            return SortFrame([], list(range(n)), [], [], [])
+        feats = to_dev(det_features, self.dev, torch.float32)
+        ctx = geometry.default_context(self.dev.index)
+        solved = 2 * n + m + 1                                                 # row_to_col | col_to_row | row_stage | solver status
+        out = torch.empty(solved + 2 * n + m, dtype=torch.int32, device=self.dev)      # ... | gate status [n] | update status [n] | new_slot [m]
+        slab = torch.empty(1, 2, n, m, dtype=torch.float64, device=self.dev)
+        base = out.data_ptr()
+        if n:
+            cost = torch.empty(n, m, dtype=torch.float64, device=self.dev)
+            ctx.check(ctx.lib.busca_appearance_cost(ctx.h, self.feat.data_ptr(), d_slot.data_ptr(), None, n, 1, feats.data_ptr(), m, E, _lib.APPEAR_MIN,
+                                                    0, cost.data_ptr(), where[1]))
+            _sframe_lib.check(flib.busca_sframe_cost(
+                self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), n, d_xyah.data_ptr(), d_tlwh.data_ptr(), m,
+                d_stale.data_ptr(), cost.data_ptr(), m, INFTY_COST, (_sframe_lib.MC if mc_lambda is not None else 0) | _sframe_lib.CLAMP,
+                0.0 if mc_lambda is None else float(mc_lambda), float(matching_threshold), float(max_iou_distance), d_first.data_ptr(),
+                d_again.data_ptr(), depth, slab.data_ptr(), base + 4 * solved, *where))
+        _assign_stages_dev(ctx, slab, up[:at], d_first, d_again, None, into=out)
+        if apply:
+            _sframe_lib.check(flib.busca_sframe_apply(
+                self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr() if n else None, n, base if n else None, base + 4 * n,
+                d_xyah.data_ptr(), _lib.ptr(d_conf), feats.data_ptr(), m, self.feat.data_ptr(), E, float(ema_alpha),
+                d_free.data_ptr() if n_free else None, n_free, base + 4 * (solved + 2 * n), base + 4 * (solved + n) if n else None, *where))
+        host = (out if apply else out[:solved + n]).cpu().numpy()              # the one device->host copy
+        _raise_flagged(host[solved:solved + n], "SortStore.frame")             # the gate's words: only rows of the cascade carry one
+        if host[solved - 1] != 0:
+            raise _lib.BuscaError("SortStore.frame: the solver ran out of its loop bounds (status %d) - is a cost -inf or a limit infinite?"
+                                  % int(host[solved - 1]))
+        if apply:
+            _raise_flagged(host[solved + n:solved + 2 * n], "SortStore.frame: update")
+        r2c, c2r, stage = host[:n], host[n:n + m], host[n + m:2 * n + m]
+        rows = [int(r) for r in np.lexsort((np.arange(n), stage)) if r2c[r] >= 0]      # by stage, then by row: the order _match lists them in
+        new = host[solved + 2 * n:] if apply else np.full(m, -1, dtype=np.int32)
+        return SortFrame([(r, int(r2c[r])) for r in rows], [int(r) for r in np.nonzero(r2c < 0)[0]], [int(j) for j in np.nonzero(c2r < 0)[0]],
+                         [(j, int(new[j])) for j in range(m) if new[j] >= 0], [j for j in range(m) if new[j] == -2])
+
+    def features(self, slots):
+        """The feature rows of the listed slots -> device float32 [n, feature_dim]; a negative entry gives the spare slot's row."""
+        slot, n = _slots_checked(slots, self.capacity, "SortStore.features")
+        if self.feature_dim is None:
+            raise ValueError("SortStore.features: the store keeps no feature rows (feature_dim)")
+        self._state()
+        return self.feat.index_select(0, self._feature_rows(slot))
+
+    def load_features(self, slots, rows):
+        """The [n, feature_dim] `rows` (host array or device tensor) into the feature rows of the listed slots as they are - not normalised: for a
+        tracker that migrates, and for tests.  A negative entry is parked in the spare slot."""
+        slot, n = _slots_checked(slots, self.capacity, "SortStore.load_features")
+        if self.feature_dim is None:
+            raise ValueError("SortStore.load_features: the store keeps no feature rows (feature_dim)")
+        shape = tuple(rows.shape) if hasattr(rows, "shape") else np.shape(rows)
+        if shape != (n, self.feature_dim):
+            raise ValueError("SortStore.load_features: %s rows for %d slots of %d values" % (shape, n, self.feature_dim))
+        rows = to_dev(rows, self.dev, torch.float32)
+        self._state()
+        if n:
+            self.feat.index_copy_(0, self._feature_rows(slot), rows)
+
+    def _feature_rows(self, slot):
+        if torch.is_tensor(slot):
+            idx = slot.to(device=self.dev, dtype=torch.int64)
+            return torch.where((idx < 0) | (idx > self.capacity), self.capacity, idx)
+        return small_to_dev(np.where(slot < 0, self.capacity, slot).astype(np.int64), self.dev, torch.int64)
 
     # ---- objects in and out
     def load(self, slots, tracks):
