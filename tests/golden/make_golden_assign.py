@@ -88,12 +88,12 @@ def reduced(c, t, x):
     return float((c[rows, x[rows]] - t).sum())
 
 
-def unique(c, t, x):
+def unique(c, t, x, margin=1e-9):
     best = reduced(c, t, x)
     for r in np.nonzero(x >= 0)[0]:
         d = c.copy()
         d[r, x[r]] = np.inf
-        if not reduced(d, t, solve_clamped(d, t)) > best + 1e-9:
+        if not reduced(d, t, solve_clamped(d, t)) > best + margin:
             return False
     return True
 
