@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so and libbusca_sframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so and libbusca_mframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -50,6 +50,12 @@ FRAME_HEADERS = ["busca_frame.h", "busca_hip.h"]
 SFRAME_OUT = os.path.join(HERE, "libbusca_sframe.so")
 SFRAME_UNITS = [("busca_sframe", False)]
 SFRAME_HEADERS = ["busca_sframe.h", "busca_hip.h"]
+# libbusca_mframe.so (include/busca_mframe.h): the context-free library of the ByteTrack frames of many sequences on one store - the ragged batched
+# forms of the two calls of libbusca_frame.so.  Handled as the six above; it compiles frame_kernel and the kernel includes below it under its own
+# mframe_kernel, so an edit there rebuilds it too.
+MFRAME_OUT = os.path.join(HERE, "libbusca_mframe.so")
+MFRAME_UNITS = [("busca_mframe", False)]
+MFRAME_HEADERS = ["busca_mframe.h", "busca_frame.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -154,13 +160,14 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the seven libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the eight libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
     _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
     _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
     _build_lib(SORT_OUT, SORT_UNITS, SORT_HEADERS, force, verbose)
     _build_lib(FRAME_OUT, FRAME_UNITS, FRAME_HEADERS, force, verbose)
     _build_lib(SFRAME_OUT, SFRAME_UNITS, SFRAME_HEADERS, force, verbose)
+    _build_lib(MFRAME_OUT, MFRAME_UNITS, MFRAME_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

@@ -1,7 +1,8 @@
 """ByteTrack's Kalman state resident on the device: the means and covariances of all tracks stay in two device tensors over `capacity` slots, and
 every step names the slots it serves.  Fronts include/busca_track.h (libbusca_track.so, bound by _track_lib) and, for the rounds of several sequences
-at once, include/busca_rounds.h (libbusca_rounds.so, bound by _rounds_lib), and for a whole frame as one chain include/busca_frame.h
-(libbusca_frame.so, bound by _frame_lib); restates what kalman.py restates -
+at once, include/busca_rounds.h (libbusca_rounds.so, bound by _rounds_lib), for a whole frame as one chain include/busca_frame.h
+(libbusca_frame.so, bound by _frame_lib), and for the frames of many sequences as one chain include/busca_mframe.h (libbusca_mframe.so, bound by
+_mframe_lib); restates what kalman.py restates -
 adapters/ByteTrack/yolox/tracker/kalman_filter.py, matching.py:132-186, byte_tracker.py:50-61,67,78,109,142-163 - without the objects: no state
 crosses PCIe in either direction, and the cost matrix of an association round is one launch."""
 import collections
@@ -9,7 +10,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _frame_lib, _lib, _rounds_lib, _track_lib, geometry
+from . import _frame_lib, _lib, _mframe_lib, _rounds_lib, _track_lib, geometry
 from ._xfer import h2d_async, small_to_dev, stream_of
 from .assignment import _assign_dev, _assign_stages_dev, _empty_triple, _solved, _triple
 from .ghost_motion import _slots_checked
@@ -26,6 +27,8 @@ RoundProblem = collections.namedtuple("RoundProblem", "slots detections det_scor
 # found the store full, and the class of every detection (0 first round, 1 second round, 2 neither)
 ByteFrame = collections.namedtuple("ByteFrame", "first second unconfirmed unmatched_pool unmatched_unconfirmed new_tracks overflow det_class")
 FRAME_STAGES = 3               # first round, second round, unconfirmed round
+# one sequence's frame in a batch (frame_batch): what frame() takes of the sequence itself - the thresholds belong to the batch
+FrameProblem = collections.namedtuple("FrameProblem", "pool_slots lost unconfirmed_slots detections det_scores free_slots", defaults=((),))
 
 
 assert (_rounds_lib.FUSE_MOTION, _rounds_lib.ONLY_POSITION, _rounds_lib.GATE_ONLY) == (_track_lib.FUSE_MOTION, _track_lib.ONLY_POSITION, _track_lib.GATE_ONLY)
@@ -69,6 +72,27 @@ def _frame_row_tables(lost, n_pool, n_unconfirmed):
     return first, again, lost
 
 
+def _stage_records(match_thresh, second_thresh, unconfirmed_thresh):
+    """The stage table of a frame's staged assignment as bytes: rounds 1 and 3 read plane 0 of the slab, round 2 plane 1."""
+    stages = np.zeros(FRAME_STAGES, dtype=np.dtype([("plane", "<i4"), ("reserved", "<i4"), ("limit", "<f8")]))
+    stages["plane"] = [0, 1, 0]
+    stages["limit"] = [float(match_thresh), float(second_thresh), float(unconfirmed_thresh)]
+    return stages.view(np.uint8).reshape(-1)
+
+
+def _byte_frame(r2c, stage, new, n_pool, lost, cls):
+    """The ByteFrame of one problem from its words of the solver (row_to_col, row_stage [n]) and of the filter (new_slot [m])."""
+    n, m = len(r2c), len(new)
+    matched = [i for i in range(n) if r2c[i] >= 0]
+    left = [i for i in range(n_pool) if r2c[i] < 0]
+    return ByteFrame([(i, int(r2c[i])) for i in matched if i < n_pool and stage[i] == 0],
+                     [(i, int(r2c[i])) for i in matched if i < n_pool and stage[i] == 1],
+                     [(i - n_pool, int(r2c[i])) for i in matched if i >= n_pool],
+                     [i for i in left if not lost[i]] + [i for i in left if lost[i]],      # the Tracked rows no round matched, then the lost ones (:364)
+                     [i - n_pool for i in range(n_pool, n) if r2c[i] < 0],
+                     [(j, int(new[j])) for j in range(m) if new[j] >= 0], [j for j in range(m) if new[j] == -2], cls)
+
+
 def _frame_detections(detections):
     """The detections of frame() on the host -> (measurements [m,4], boxes [m,4]).  Objects give tlwh_to_xyah(.tlwh) and .tlbr, as everywhere; a
     host [m,4] array is taken as (x, y, a, h) measurements, exactly, and the boxes follow as STrack.tlbr derives them from a state."""
@@ -94,6 +118,8 @@ class KalmanStore:
                                      RoundProblem, one launch per step and one copy back whatever its length (busca_rounds_cost)
       frame(pool, lost, unconfirmed, dets, scores, ...)   a whole BYTETracker.update on the state: predict, the three rounds as one staged
                                      assignment, update and initiation -> ByteFrame; four launches and one copy home whatever the track count
+      frame_batch(problems, ...)     the frames of one time step of many sequences that share the store: a list of FrameProblem, the same four
+                                     launches and one copy home whatever its length (busca_mframe_cost, busca_mframe_apply) -> [ByteFrame]
       load / store(slots, stracks)   states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
     `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors, allocated at the first call that needs them; the slot behind
     the last is a spare no kernel writes (the kernels are told `capacity`), where load / store park the negative entries of a slot list.
@@ -101,7 +127,7 @@ class KalmanStore:
     entry is skipped.  A slot list given as a device tensor is not read back: it is the caller's to keep distinct, and entries outside the capacity
     are skipped by the kernels and touch no memory.  Detections: objects with `.tlwh` (and `.tlbr` for cost / round), a host [m,4] array or device
     tensor of (x, y, a, h) measurements where only those are needed, or what detections() returned.  Every call is asynchronous on torch's
-    current stream of the device, except that round(), round_batch(), load() of nothing and store() wait for their one copy."""
+    current stream of the device, except that round(), round_batch(), frame(), frame_batch(), load() of nothing and store() wait for their one copy."""
 
     def __init__(self, capacity, device=None):
         capacity = int(capacity)
@@ -393,10 +419,10 @@ class KalmanStore:
                 for k, (n, m) in enumerate(dims)]
 
     # ---- a whole frame as one chain (busca_frame.h, libbusca_frame.so; busca_assign_stages)
-    def _frame_checked(self, pool_slots, lost, unconfirmed_slots, free_slots, detections, det_scores, track_thresh, low_thresh):
+    def _frame_checked(self, pool_slots, lost, unconfirmed_slots, free_slots, detections, det_scores, track_thresh, low_thresh,
+                       what="KalmanStore.frame"):
         """The host side of frame(), before anything is allocated -> (rows int32 [n]: pool then unconfirmed, n_pool, first, again, lost, free int32,
-        scores float64 [m], classes uint8 [m], measurements [m,4], boxes [m,4])."""
-        what = "KalmanStore.frame"
+        scores float64 [m], classes uint8 [m], measurements [m,4], boxes [m,4]).  `what` names the call (and, from frame_batch, the problem)."""
         lists = []
         for name, x in (("pool_slots", pool_slots), ("unconfirmed_slots", unconfirmed_slots), ("free_slots", free_slots)):
             if torch.is_tensor(x):
@@ -446,13 +472,10 @@ class KalmanStore:
                                                                                   det_scores, track_thresh, low_thresh)
         n, m, n_free = len(rows), len(xyah), len(free)
         # one pinned upload of every small table: the 16-byte stage records first, then the int32 tables, then the `lost` bytes
-        stages = np.zeros(FRAME_STAGES, dtype=np.dtype([("plane", "<i4"), ("reserved", "<i4"), ("limit", "<f8")]))
-        stages["plane"] = [0, 1, 0]
-        stages["limit"] = [float(match_thresh), float(second_thresh), float(unconfirmed_thresh)]
         ints = np.concatenate([rows, first, again, free]).astype(np.int32)
         flags = np.zeros(-(-n_pool // 4) * 4, dtype=np.uint8)
         flags[:n_pool] = lost
-        up = h2d_async(np.concatenate([stages.view(np.uint8).reshape(-1), ints.view(np.uint8), flags]), self.dev)
+        up = h2d_async(np.concatenate([_stage_records(match_thresh, second_thresh, unconfirmed_thresh), ints.view(np.uint8), flags]), self.dev)
         at = 16 * FRAME_STAGES
         words = up[at:at + 4 * len(ints)].view(torch.int32)
         d_slot, d_first, d_again, d_free = words[:n], words[n:2 * n], words[2 * n:3 * n], words[3 * n:]
@@ -463,11 +486,9 @@ class KalmanStore:
             _track_lib.check(lib.busca_track_kalman_predict(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), d_lost.data_ptr(),
                                                             n_pool, *where))
 
-        def pool_left(r2c):                                                    # the Tracked rows no round matched, then the lost ones (:364)
-            return [i for i in range(n_pool) if r2c[i] < 0 and not lost[i]] + [i for i in range(n_pool) if r2c[i] < 0 and lost[i]]
         if m == 0:
             none = -np.ones(n, dtype=np.int64)
-            return ByteFrame([], [], [], pool_left(none), list(range(n - n_pool)), [], [], cls)
+            return _byte_frame(none, none, none[:0], n_pool, lost, cls)
         # one upload of the detection table: measurements, boxes, scores, and the class bytes behind them
         tail = np.zeros(-(-m // 8) * 8, dtype=np.uint8)
         tail[:m] = cls
@@ -494,14 +515,119 @@ class KalmanStore:
             raise _lib.BuscaError("KalmanStore.frame: the solver ran out of its loop bounds (status %d) - is a cost -inf or a limit infinite?"
                                   % int(host[solved - 1]))
         _raise_flagged(host[solved:solved + n], "KalmanStore.frame")
-        r2c, stage = host[:n], host[n + m:2 * n + m]
-        matched = [i for i in range(n) if r2c[i] >= 0]
         new = host[solved + n:] if apply else np.full(m, -1, dtype=np.int32)
-        return ByteFrame([(i, int(r2c[i])) for i in matched if i < n_pool and stage[i] == 0],
-                         [(i, int(r2c[i])) for i in matched if i < n_pool and stage[i] == 1],
-                         [(i - n_pool, int(r2c[i])) for i in matched if i >= n_pool],
-                         pool_left(r2c), [i - n_pool for i in range(n_pool, n) if r2c[i] < 0],
-                         [(j, int(new[j])) for j in range(m) if new[j] >= 0], [j for j in range(m) if new[j] == -2], cls)
+        return _byte_frame(host[:n], host[n + m:2 * n + m], new, n_pool, lost, cls)
+
+    # ---- the frames of many sequences as one chain (busca_mframe.h, libbusca_mframe.so; busca_assign_stages over the batch)
+    def _frame_batch_checked(self, problems, track_thresh, low_thresh):
+        """The host side of frame_batch(), before anything is allocated -> [what _frame_checked returns, per problem]."""
+        what = "KalmanStore.frame_batch"
+        problems = [p if isinstance(p, FrameProblem) else FrameProblem(*p) for p in problems]
+        if len(problems) > _mframe_lib.MAX_BATCH:
+            raise ValueError("%s: %d problems, one call takes %d" % (what, len(problems), _mframe_lib.MAX_BATCH))
+        checked = []
+        for k, p in enumerate(problems):
+            name = "%s: problem %d" % (what, k)
+            try:
+                checked.append(self._frame_checked(p.pool_slots, p.lost, p.unconfirmed_slots, p.free_slots, p.detections, p.det_scores, track_thresh,
+                                                   low_thresh, what=name))
+            except ValueError as e:
+                if name in str(e):
+                    raise
+                raise ValueError("%s: %s" % (name, e)) from None
+        if len(checked) > 1:                                                   # one launch serves them all: what two problems share, two workgroups race on
+            rows = np.concatenate([c[0] for c in checked])
+            taken = np.concatenate([rows[rows >= 0]] + [c[5] for c in checked])
+            if len(np.unique(taken)) != len(taken):
+                slots, count = np.unique(taken, return_counts=True)
+                raise ValueError("%s: the tracks and the free slots must be distinct across the whole batch (slot %d is listed twice)"
+                                 % (what, int(slots[count > 1][0])))
+        return checked
+
+    def frame_batch(self, problems, track_thresh, match_thresh, det_thresh, mot20=False, low_thresh=0.1, second_thresh=0.5, unconfirmed_thresh=0.7,
+                    apply=True):
+        """frame() of every FrameProblem(pool_slots, lost, unconfirmed_slots, detections, det_scores, free_slots) of a list - the frames of one time
+        step of many sequences that share this store - as ONE chain on the stream -> [ByteFrame], each what frame() returns for that problem alone,
+        the states bit for bit what the frames one after the other leave.  Whatever the number of problems: one pinned upload of every small table,
+        one float64 upload of the concatenated detection table, STrack.multi_predict over all pool rows (busca_track_kalman_predict; the
+        unconfirmed rows stand as -1 in its list), busca_mframe_cost, busca_assign_stages over the batch with its `dims`, busca_mframe_apply, and
+        ONE device->host copy of B (3 N + 2 M + 1) words, N and M the largest row and detection counts; the host reads the matches after the filter
+        has been enqueued.  The thresholds and `mot20` are the batch's, as the solver's stage table is; the rounds of the detections follow from
+        each problem's scores.  The tracks and the free slots must be distinct across the whole batch (ValueError, before anything is allocated).
+        An empty list gives []; without any detection only the prediction happens and nothing is copied.  Raises BuscaError on a solver status and
+        LinAlgError where an update finds a projected covariance that is not positive definite, naming the problem (and the track), after the
+        whole batch has been applied.  For a single sequence frame() is the shorter route."""
+        checked = self._frame_batch_checked(problems, track_thresh, low_thresh)
+        B = len(checked)
+        if B == 0:
+            return []
+        W = _mframe_lib.PROBLEM_WORDS
+        n_k, m_k, f_k = ([len(c[i]) for c in checked] for i in (0, 8, 5))
+        N, M = max(n_k), max(m_k)
+        n_total, m_total, f_total = sum(n_k), sum(m_k), sum(f_k)
+        table = np.zeros((B, W), dtype=np.int32)                               # row_begin, n_k, det_begin, m_k, free_begin, n_free_k
+        table[:, 1], table[:, 3], table[:, 5] = n_k, m_k, f_k
+        table[1:, 0::2] = np.cumsum(table[:-1, 1::2], axis=0)
+        first, again = (np.full((B, N), -1, dtype=np.int32) for _ in range(2))
+        predict, flags = np.full(n_total, -1, dtype=np.int32), np.zeros(-(-n_total // 4) * 4, dtype=np.uint8)
+        for k, (rows, n_pool, fst, agn, lost) in enumerate(c[:5] for c in checked):
+            first[k, :n_k[k]], again[k, :n_k[k]] = fst, agn
+            at = table[k, 0]
+            predict[at:at + n_pool], flags[at:at + n_pool] = rows[:n_pool], lost      # the unconfirmed rows are matched but never predicted: -1
+        # one pinned upload of every small table: the 16-byte stage records first, then the int32 tables, then the `lost` bytes
+        parts = [np.concatenate([c[0] for c in checked]), predict, table.reshape(-1), table[:, 1::2][:, :2].reshape(-1), first.reshape(-1),
+                 again.reshape(-1), np.concatenate([c[5] for c in checked])]
+        ints = np.concatenate(parts).astype(np.int32)
+        up = h2d_async(np.concatenate([_stage_records(match_thresh, second_thresh, unconfirmed_thresh), ints.view(np.uint8), flags]), self.dev)
+        at = 16 * FRAME_STAGES
+        d_slot, d_predict, d_table, d_dims, d_first, d_again, d_free = up[at:at + 4 * len(ints)].view(torch.int32).split([len(p) for p in parts])
+        d_lost = up[at + 4 * len(ints):]
+        lib = self._state()
+        where = self._where()
+        if any(c[1] for c in checked):
+            _track_lib.check(lib.busca_track_kalman_predict(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_predict.data_ptr(),
+                                                            d_lost.data_ptr(), n_total, *where))
+        none = -np.ones(N, dtype=np.int64)
+        if M == 0:
+            return [_byte_frame(none[:n], none[:n], none[:0], c[1], c[4], c[7]) for n, c in zip(n_k, checked)]
+        # one upload of the detection table: measurements, boxes, scores, and the class bytes behind them
+        tail = np.zeros(-(-m_total // 8) * 8, dtype=np.uint8)
+        tail[:m_total] = np.concatenate([c[7] for c in checked])
+        dets = small_to_dev(np.concatenate([c[8].reshape(-1) for c in checked] + [c[9].reshape(-1) for c in checked] + [c[6] for c in checked]
+                                           + [tail.view(np.float64)]), self.dev, torch.float64)
+        d_xyah, d_tlbr, d_score, d_cls = dets[:4 * m_total], dets[4 * m_total:8 * m_total], dets[8 * m_total:9 * m_total], dets[9 * m_total:].view(torch.uint8)
+        solved = B * (2 * N + M + 1)                                           # row_to_col [B,N] | col_to_row [B,M] | row_stage [B,N] | solver status [B]
+        out = torch.empty(solved + B * (N + M), dtype=torch.int32, device=self.dev)      # ... | update status [B,N] | new_slot [B,M]: one copy
+        slab = torch.empty(B, 2, N, M, dtype=torch.float64, device=self.dev)
+        mlib = _mframe_lib.load()
+        base = out.data_ptr()
+        if N:
+            _mframe_lib.check(mlib.busca_mframe_cost(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), n_total, d_tlbr.data_ptr(),
+                                                     None if mot20 else d_score.data_ptr(), d_cls.data_ptr(), m_total, f_total, d_table.data_ptr(), B, N, M,
+                                                     slab.data_ptr(), base + 4 * solved, *where))
+        _assign_stages_dev(geometry.default_context(self.dev.index), slab, up[:at], d_first, d_again, d_dims, into=out)
+        if apply:
+            _mframe_lib.check(mlib.busca_mframe_apply(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr() if n_total else None,
+                                                      n_total, base if N else None, base + 4 * B * N, d_xyah.data_ptr(), d_score.data_ptr(),
+                                                      d_cls.data_ptr(), m_total, float(det_thresh), d_free.data_ptr() if f_total else None, f_total,
+                                                      d_table.data_ptr(), B, N, M, base + 4 * (solved + B * N), base + 4 * solved if N else None, *where))
+        host = (out if apply else out[:solved]).cpu().numpy()                  # the one device->host copy
+        # the words of problem k are the corner (n_k, m_k) of its blocks: the kernels write nothing else, and nothing else is read
+        r2c, _, stage, status = np.split(host[:solved], [B * N, B * (N + M), B * (2 * N + M)])
+        r2c, stage = r2c.reshape(B, N), stage.reshape(B, N)
+        for k in range(B):
+            if status[k] != 0:
+                raise _lib.BuscaError("KalmanStore.frame_batch: problem %d: the solver ran out of its loop bounds (status %d) - is a cost -inf or a limit "
+                                      "infinite?" % (k, int(status[k])))
+        frames = []
+        if apply:
+            flagged, new = host[solved:solved + B * N].reshape(B, N), host[solved + B * N:].reshape(B, M)
+            for k in range(B):
+                _raise_flagged(flagged[k, :n_k[k]], "KalmanStore.frame_batch: problem %d" % k)
+        for k, c in enumerate(checked):
+            started = new[k, :m_k[k]] if apply else np.full(m_k[k], -1, dtype=np.int32)
+            frames.append(_byte_frame(r2c[k, :n_k[k]], stage[k, :n_k[k]], started, c[1], c[4], c[7]))
+        return frames
 
     # ---- objects in and out
     def _rows(self, slots, stracks, what):

@@ -4,7 +4,7 @@ each name is defined in the module of its family and re-exported here as the sam
   kalman        ByteTrack's Kalman filter, gating, the predicted cost of a round                               (busca_hip.h)
   kalman_store  the same filter on state that stays on the device: slots, rounds without a state copy          (busca_track.h, libbusca_track.so;
                 the rounds of many sequences in one launch: busca_rounds.h, libbusca_rounds.so; a whole frame as one chain:
-                busca_frame.h, libbusca_frame.so)
+                busca_frame.h, libbusca_frame.so; the frames of many sequences as one chain: busca_mframe.h, libbusca_mframe.so)
   sort_store    StrongSORT's filter on state that stays on the device: NSA update, camera update, gated rounds, (busca_sort.h, libbusca_sort.so;
                 Tracker._match as one staged assignment; a whole frame with the feature rows as one chain       busca_sframe.h, libbusca_sframe.so)
   assignment    linear assignment, min-cost matching, the matching cascade, associate_round, staged assignment (busca_assign.h, busca_assign_stages.h)
@@ -35,7 +35,7 @@ from .ghost_gallery import GhostGallery  # noqa: F401
 from .ghost_motion import GhostMotion, ghost_motion_check_config  # noqa: F401
 from .kalman import (CHI2INV95, TRACKED, fuse_motion, gate_cost_matrix, gating_distance, multi_initiate, multi_predict, multi_update,  # noqa: F401
                      predicted_cost, tlwh_to_xyah)
-from .kalman_store import ByteFrame, KalmanStore, RoundProblem  # noqa: F401
+from .kalman_store import ByteFrame, FrameProblem, KalmanStore, RoundProblem  # noqa: F401
 from .sort_store import SortFrame, SortStore  # noqa: F401
 from .track_boxes import (center_distance, get_detection_coverage, iou_distance, is_reliable, missing_candidate_bbox, recover_with_busca,  # noqa: F401
                           remove_duplicate_stracks, warp_pos)
