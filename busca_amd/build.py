@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so and libbusca_mframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so, libbusca_mframe.so and libbusca_msframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -56,6 +56,12 @@ SFRAME_HEADERS = ["busca_sframe.h", "busca_hip.h"]
 MFRAME_OUT = os.path.join(HERE, "libbusca_mframe.so")
 MFRAME_UNITS = [("busca_mframe", False)]
 MFRAME_HEADERS = ["busca_mframe.h", "busca_frame.h", "busca_hip.h"]
+# libbusca_msframe.so (include/busca_msframe.h): the context-free library of the StrongSORT frames of many sequences on one store - the ragged batched
+# forms of the three calls of libbusca_sframe.so, with the appearance tile of busca_appearance_cost inside the cost kernel.  Handled as the seven
+# above; it compiles sframe_kernel, appear_kernel and the kernel includes below them under its own msframe_kernel, so an edit there rebuilds it too.
+MSFRAME_OUT = os.path.join(HERE, "libbusca_msframe.so")
+MSFRAME_UNITS = [("busca_msframe", False)]
+MSFRAME_HEADERS = ["busca_msframe.h", "busca_sframe.h", "busca_appearance.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -160,7 +166,7 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the eight libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the nine libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
     _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
     _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
@@ -168,6 +174,7 @@ def build(force=False, verbose=False):
     _build_lib(FRAME_OUT, FRAME_UNITS, FRAME_HEADERS, force, verbose)
     _build_lib(SFRAME_OUT, SFRAME_UNITS, SFRAME_HEADERS, force, verbose)
     _build_lib(MFRAME_OUT, MFRAME_UNITS, MFRAME_HEADERS, force, verbose)
+    _build_lib(MSFRAME_OUT, MSFRAME_UNITS, MSFRAME_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

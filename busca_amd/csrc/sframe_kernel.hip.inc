@@ -13,15 +13,18 @@
 //      among such columns is counted by the workgroup itself over the columns below j, as frame_apply_kernel counts it.  Both decisions are
 //      uniform over the workgroup.
 //
+// The bodies are device functions - sframe_advance_track, sframe_stage_row / sframe_stage_dets / sframe_entry, sframe_apply_row / sframe_apply_col -
+// which msframe_kernel.hip.inc (libbusca_msframe.so) calls once per (problem, row), (problem, tile) and (problem, column) of a batch: one text behind
+// two addressings.
+//
 // No multiply-add contraction anywhere in this file (store_kernel.hip.inc, included last, leaves the file-scope mode at `fast`).
 #pragma clang fp contract(off)
 
-__global__ void __launch_bounds__(64) sframe_advance_kernel(KStore k, const double* __restrict__ matrix) {
-    const int t = blockIdx.x, tid = threadIdx.x;
-    int s;
-    if (t >= k.n || !kstore_live(k, t, s)) return;                 // uniform over the workgroup
-    double* pm = k.mean + (size_t)s * 8;
-    sort_predict_track(pm, k.cov + (size_t)s * 64, tid);
+// Track.predict of the state at (pm, pc) and, with a warp, Track.camera_update of the predicted mean by lane 0.  All 64 lanes of the workgroup call it
+// (with a warp it holds a barrier).  sframe_advance_kernel and msframe_advance_kernel (msframe_kernel.hip.inc, libbusca_msframe.so) are this function
+// behind two addressings.
+__device__ __forceinline__ void sframe_advance_track(double* pm, double* pc, const double* __restrict__ matrix, int tid) {
+    sort_predict_track(pm, pc, tid);
     if (matrix == nullptr) return;
     __syncthreads();                                               // the predicted mean is lanes 0 .. 7's
     if (tid != 0) return;
@@ -35,6 +38,13 @@ __global__ void __launch_bounds__(64) sframe_advance_kernel(KStore k, const doub
     pm[1] = y1 + h / 2;
     pm[2] = w / h;
     pm[3] = h;
+}
+
+__global__ void __launch_bounds__(64) sframe_advance_kernel(KStore k, const double* __restrict__ matrix) {
+    const int t = blockIdx.x, tid = threadIdx.x;
+    int s;
+    if (t >= k.n || !kstore_live(k, t, s)) return;                 // uniform over the workgroup
+    sframe_advance_track(k.mean + (size_t)s * 8, k.cov + (size_t)s * 64, matrix, tid);
 }
 
 struct SFrameCost {
@@ -53,90 +63,110 @@ struct SFrameCost {
 
 #define SFRAME_UNREAD 3         // a row state: no stage reads this plane of the row
 
-__global__ void __launch_bounds__(256) sframe_cost_kernel(KStore k, SFrameCost a) {
-    __shared__ double smu[PW_TA][4], sL[PW_TA][4][4], sbox[PW_TA][4];
-    __shared__ int sgate[PW_TA];                                   // plane 0: 0 a good track, 1 S not positive definite, 2 skipped, 3 not read
-    __shared__ int siou[PW_TA];                                    // plane 1: 0 a row of IoU costs, 2 stale or skipped, 3 not read
-    __shared__ double sz[PW_TB][4], sb[PW_TB][4];
-    const int tid = threadIdx.x, a0 = blockIdx.y * PW_TA, b0 = blockIdx.x * PW_TB;
-    if (tid < PW_TA) {
-        const int t = a0 + tid;
-        int gate = SFRAME_UNREAD, iou = SFRAME_UNREAD;
-        if (t < k.n) {
-            const int f = a.first[t], g = a.again != nullptr ? a.again[t] : -1;
-            int s;
-            const bool live = kstore_live(k, t, s);
-            if (f >= 0 && f < a.depth) {
-                gate = 2;
-                if (live) {
-                    double mu[4], L[4][4];
-                    gate = kalman_gate_factor(k.mean + (size_t)s * 8, k.cov + (size_t)s * 64, 0, 0, mu, L) ? 0 : 1;
+// what a workgroup stages of its PW_TA x PW_TB tile, in LDS
+struct SFrameTile {
+    double mu[PW_TA][4], L[PW_TA][4][4], box[PW_TA][4];
+    int gate[PW_TA];                                               // plane 0: 0 a good track, 1 S not positive definite, 2 skipped, 3 not read
+    int iou[PW_TA];                                                // plane 1: 0 a row of IoU costs, 2 stale or skipped, 3 not read
+    double z[PW_TB][4], b[PW_TB][4];
+};
+
+// Row r of the tile, row t of the list k.slot[0 .. k.n) (t >= k.n: a row that is not there), staged by one lane: the projected mean, the Cholesky
+// factor and the tlwh box, each only where the row's stage reads that plane.  `a.first`, `a.again`, `a.stale` and `a.status` are indexed by t; the
+// status word is written where `with_status` (the tiles of column block 0).
+__device__ __forceinline__ void sframe_stage_row(SFrameTile& T, const KStore& k, const SFrameCost& a, int r, int t, bool with_status) {
+    int gate = SFRAME_UNREAD, iou = SFRAME_UNREAD;
+    if (t < k.n) {
+        const int f = a.first[t], g = a.again != nullptr ? a.again[t] : -1;
+        int s;
+        const bool live = kstore_live(k, t, s);
+        if (f >= 0 && f < a.depth) {
+            gate = 2;
+            if (live) {
+                double mu[4], L[4][4];
+                gate = kalman_gate_factor(k.mean + (size_t)s * 8, k.cov + (size_t)s * 64, 0, 0, mu, L) ? 0 : 1;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        smu[tid][i] = mu[i];
+                for (int i = 0; i < 4; ++i) {
+                    T.mu[r][i] = mu[i];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) sL[tid][i][j] = L[i][j];
-                    }
+                    for (int j = 0; j < 4; ++j) T.L[r][i][j] = L[i][j];
                 }
             }
-            if (f == a.depth || g == a.depth) {
-                iou = 2;
-                if (live && !(a.stale != nullptr && a.stale[t])) {
-                    double b[4];
-                    kalman_box_of(k.mean + (size_t)s * 8, 0, b);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) sbox[tid][i] = b[i];
-                    iou = 0;
-                }
-            }
-            if (b0 == 0 && a.status != nullptr) a.status[t] = gate == 1 ? 1 : 0;
         }
-        sgate[tid] = gate;
-        siou[tid] = iou;
+        if (f == a.depth || g == a.depth) {
+            iou = 2;
+            if (live && !(a.stale != nullptr && a.stale[t])) {
+                double b[4];
+                kalman_box_of(k.mean + (size_t)s * 8, 0, b);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) T.box[r][i] = b[i];
+                iou = 0;
+            }
+        }
+        if (with_status && a.status != nullptr) a.status[t] = gate == 1 ? 1 : 0;
     }
-    {
-        const int r = b0 + tid / 4;
-        sz[tid / 4][tid % 4] = r < a.m ? a.det_xyah[(size_t)r * 4 + tid % 4] : 0.0;
-        sb[tid / 4][tid % 4] = r < a.m ? a.det_tlwh[(size_t)r * 4 + tid % 4] : 0.0;
+    T.gate[r] = gate;
+    T.iou[r] = iou;
+}
+
+// the detections b0 .. b0 + PW_TB - 1 of a.m, by all 256 lanes
+__device__ __forceinline__ void sframe_stage_dets(SFrameTile& T, const SFrameCost& a, int b0, int tid) {
+    const int r = b0 + tid / 4;
+    T.z[tid / 4][tid % 4] = r < a.m ? a.det_xyah[(size_t)r * 4 + tid % 4] : 0.0;
+    T.b[tid / 4][tid % 4] = r < a.m ? a.det_tlwh[(size_t)r * 4 + tid % 4] : 0.0;
+}
+
+// The entry (row ri, column col) of the staged tile in both planes.  `appear`: where the appearance cost of the pair stands; it is read only for a
+// good track whose gate admits the pair.
+__device__ __forceinline__ void sframe_entry(const SFrameTile& T, const SFrameCost& a, int ri, int col, const double* __restrict__ appear, double& v0,
+                                             double& v1) {
+    const int gate = T.gate[ri], iou = T.iou[ri];
+    v0 = INFINITY, v1 = INFINITY;
+    if (gate != SFRAME_UNREAD) {                                   // sort_gate_cost_kernel's entry
+        double v;
+        if (gate == 2) v = a.gated_cost;
+        else if (gate == 1) v = __builtin_nan("");
+        else {
+            double d[4], L[4][4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                d[c] = T.z[col][c] - T.mu[ri][c];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) L[c][e] = T.L[ri][c][e];
+            }
+            const double g = kalman_gate_one<4>(L, d, 0);
+            v = g > 9.4877 ? a.gated_cost : *appear;               // chi2inv95[4]
+            if (a.flags & SORT_MC) v = a.lambda * v + a.rest * g;
+        }
+        v0 = sort_clamp(v, a.flags, a.max_distance, a.limit);
     }
+    if (iou != SFRAME_UNREAD) {                                    // sort_iou_cost_kernel's entry
+        double v = SORT_INFTY_COST;
+        if (iou == 0) {
+            const double t[4] = {T.box[ri][0], T.box[ri][1], T.box[ri][2], T.box[ri][3]};
+            const double b[4] = {T.b[col][0], T.b[col][1], T.b[col][2], T.b[col][3]};
+            v = sort_iou_cost(t, b);
+        }
+        v1 = sort_clamp(v, SORT_CLAMP, a.max_iou, a.iou_limit);
+    }
+}
+
+__global__ void __launch_bounds__(256) sframe_cost_kernel(KStore k, SFrameCost a) {
+    __shared__ SFrameTile T;
+    const int tid = threadIdx.x, a0 = blockIdx.y * PW_TA, b0 = blockIdx.x * PW_TB;
+    if (tid < PW_TA) sframe_stage_row(T, k, a, tid, a0 + tid, b0 == 0);
+    sframe_stage_dets(T, a, b0, tid);
     __syncthreads();
     const int col = tid & 63, rg = tid >> 6;
     const int j = b0 + col;
     if (j >= a.m) return;
-    const double b[4] = {sb[col][0], sb[col][1], sb[col][2], sb[col][3]};
     const size_t plane = (size_t)k.n * (size_t)a.m;
 #pragma unroll
     for (int q = 0; q < PW_TA / 4; ++q) {
         const int ri = rg + 4 * q, i = a0 + ri;
         if (i >= k.n) continue;
-        const int gate = sgate[ri], iou = siou[ri];
-        double v0 = INFINITY, v1 = INFINITY;
-        if (gate != SFRAME_UNREAD) {                               // sort_gate_cost_kernel's entry
-            double v;
-            if (gate == 2) v = a.gated_cost;
-            else if (gate == 1) v = __builtin_nan("");
-            else {
-                double d[4], L[4][4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    d[c] = sz[col][c] - smu[ri][c];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) L[c][e] = sL[ri][c][e];
-                }
-                const double g = kalman_gate_one<4>(L, d, 0);
-                v = g > 9.4877 ? a.gated_cost : a.cost[(size_t)i * a.ld_cost + j];      // chi2inv95[4]
-                if (a.flags & SORT_MC) v = a.lambda * v + a.rest * g;
-            }
-            v0 = sort_clamp(v, a.flags, a.max_distance, a.limit);
-        }
-        if (iou != SFRAME_UNREAD) {                                // sort_iou_cost_kernel's entry
-            double v = SORT_INFTY_COST;
-            if (iou == 0) {
-                const double t[4] = {sbox[ri][0], sbox[ri][1], sbox[ri][2], sbox[ri][3]};
-                v = sort_iou_cost(t, b);
-            }
-            v1 = sort_clamp(v, SORT_CLAMP, a.max_iou, a.iou_limit);
-        }
+        double v0, v1;
+        sframe_entry(T, a, ri, col, a.cost + ((size_t)i * a.ld_cost + j), v0, v1);
         const size_t at = (size_t)i * a.m + j;
         a.out[at] = v0;
         a.out[plane + at] = v1;
@@ -201,22 +231,21 @@ __device__ __forceinline__ void sframe_ema_feature(float* row, const float* __re
     }
 }
 
-__global__ void __launch_bounds__(64) sframe_apply_kernel(KStore k, SFrameApply f) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (b < k.n) {                                                 // a row: Track.update with its match
-        int s;
-        const int j = f.row_to_col[b];
-        if (!kstore_live(k, b, s) || j < 0 || j >= f.m) {          // uniform over the workgroup
-            if (tid == 0 && f.status != nullptr) f.status[b] = 0;
-            return;
-        }
-        sframe_ema_feature(f.feat + (size_t)s * f.E, f.det_feat + (size_t)j * f.E, f.wa, f.wb, f.E, tid);
-        sort_update_track(k.mean + (size_t)s * 8, k.cov + (size_t)s * 64, f.det_xyah + (size_t)j * 4, f.det_conf != nullptr ? f.det_conf[j] : 0.0,
-                          f.status != nullptr ? f.status + b : nullptr, tid);
+// Row b of the list: Track.update of slot[b] with its match.  All 64 lanes of the workgroup call it.
+__device__ __forceinline__ void sframe_apply_row(const KStore& k, const SFrameApply& f, int b, int tid) {
+    int s;
+    const int j = f.row_to_col[b];
+    if (!kstore_live(k, b, s) || j < 0 || j >= f.m) {              // uniform over the workgroup
+        if (tid == 0 && f.status != nullptr) f.status[b] = 0;
         return;
     }
-    const int j = b - k.n;                                         // a column: Tracker._initiate_track
-    if (j >= f.m) return;
+    sframe_ema_feature(f.feat + (size_t)s * f.E, f.det_feat + (size_t)j * f.E, f.wa, f.wb, f.E, tid);
+    sort_update_track(k.mean + (size_t)s * 8, k.cov + (size_t)s * 64, f.det_xyah + (size_t)j * 4, f.det_conf != nullptr ? f.det_conf[j] : 0.0,
+                      f.status != nullptr ? f.status + b : nullptr, tid);
+}
+
+// Column j < f.m: Tracker._initiate_track, ranked among the unmatched columns below j of f.col_to_row.  All 64 lanes of the workgroup call it.
+__device__ __forceinline__ void sframe_apply_col(const KStore& k, const SFrameApply& f, int j, int tid) {
     if (f.col_to_row[j] >= 0) {
         if (tid == 0) f.new_slot[j] = -1;
         return;
@@ -234,4 +263,15 @@ __global__ void __launch_bounds__(64) sframe_apply_kernel(KStore k, SFrameApply 
     if (s < 0 || s >= k.S) return;
     sframe_first_feature(f.feat + (size_t)s * f.E, f.det_feat + (size_t)j * f.E, f.E, tid);
     kalman_initiate_track(f.det_xyah + (size_t)j * 4, k.mean + (size_t)s * 8, k.cov + (size_t)s * 64, tid);
+}
+
+__global__ void __launch_bounds__(64) sframe_apply_kernel(KStore k, SFrameApply f) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b < k.n) {
+        sframe_apply_row(k, f, b, tid);
+        return;
+    }
+    const int j = b - k.n;
+    if (j >= f.m) return;
+    sframe_apply_col(k, f, j, tid);
 }

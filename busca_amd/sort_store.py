@@ -1,7 +1,8 @@
 """StrongSORT's Kalman state resident on the device: the means and covariances of all tracks stay in two device tensors over `capacity` slots, and
 every step names the slots it serves.  Fronts include/busca_sort.h (libbusca_sort.so, bound by _sort_lib), for the two steps whose arithmetic is
 ByteTrack's (initiate, the box conversions) include/busca_track.h through a KalmanStore over the same tensors, and for a whole frame as one chain
-include/busca_sframe.h (libbusca_sframe.so, bound by _sframe_lib).  Restates Track.predict / update /
+include/busca_sframe.h (libbusca_sframe.so, bound by _sframe_lib), and for the frames of many sequences on one store include/busca_msframe.h
+(libbusca_msframe.so, bound by _msframe_lib).  Restates Track.predict / update /
 camera_update (adapters/StrongSORT/deep_sort/track.py:202-250), gate_cost_matrix with min_cost_matching's clamp (linear_assignment.py:61,164-210)
 and the two stages of Tracker._match (tracker.py:211-248) without the objects.  deep_sort/kalman_filter.py and iou_matching.py are not in the
 reference tree: predict, the confidence-scaled update and iou_cost are restated from upstream StrongSORT (DESIGN K-SORT)."""
@@ -10,7 +11,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, _sframe_lib, _sort_lib, geometry
+from . import _lib, _msframe_lib, _sframe_lib, _sort_lib, geometry
 from ._xfer import h2d_async, small_to_dev, stream_of, to_dev
 from .appearance import INFTY_COST
 from .assignment import _assign_dev, _assign_stages_dev, _solved
@@ -23,9 +24,13 @@ from .kalman_store import KalmanStore, _small
 # stage; rows index `slots`), the rows and the detections nothing matched, the tracks started as (detection, slot), and the detections that would have
 # started one but found the store full
 SortFrame = collections.namedtuple("SortFrame", "matches unmatched_tracks unmatched_detections new_tracks overflow")
+# one frame of SortStore.frame_batch: the arguments of frame() that belong to a sequence - its tracks, its detections, its free slots, its camera matrix
+SortFrameProblem = collections.namedtuple("SortFrameProblem", "slots time_since_update confirmed det_tlwh det_confidence det_features free_slots camera_matrix",
+                                          defaults=((), None))
 APPEAR_E_MIN, APPEAR_E_MAX = 16, 2048      # BUSCA_APPEAR_E_MIN / _MAX: the feature widths busca_appearance_cost takes (multiples of 16)
 
-assert (_sframe_lib.MC, _sframe_lib.CLAMP) == (_sort_lib.MC, _sort_lib.CLAMP)
+assert (_sframe_lib.MC, _sframe_lib.CLAMP) == (_sort_lib.MC, _sort_lib.CLAMP) == (_msframe_lib.MC, _msframe_lib.CLAMP)
+assert (_msframe_lib.E_MIN, _msframe_lib.E_MAX, _msframe_lib.MAX_DETS) == (APPEAR_E_MIN, APPEAR_E_MAX, _sframe_lib.MAX_DETS)
 
 
 def _frame_boxes(det_tlwh):
@@ -84,6 +89,8 @@ class SortStore:
       match(metric, slots, ...)              the whole of Tracker._match - cascade, IoU stage, merge - as one staged assignment; ONE copy whatever the depth
       frame(slots, ...)                      a whole frame on the state and the feature rows: predict, camera update, _match, update and initiation as
                                              ONE chain -> SortFrame; needs `feature_dim`
+      frame_batch(problems, ...)             the frames of one time step of many sequences that share the store: a list of SortFrameProblem, the same
+                                             chain once for all of them -> [SortFrame]
       features / load_features(slots, ...)   the feature rows of the listed slots, out and in
       load / store(slots, tracks)            states from / to objects with `.mean` / `.covariance`, for a tracker that migrates call by call
     `mean` [capacity + 1, 8] and `cov` [capacity + 1, 8, 8] are float64 device tensors in the layout of KalmanStore, allocated at the first call that
@@ -378,10 +385,9 @@ class SortStore:
 
     # ---- a whole frame as one chain (busca_sframe.h, libbusca_sframe.so; busca_appearance_cost, busca_assign_stages)
     def _frame_checked(self, slots, time_since_update, confirmed, det_tlwh, det_confidence, det_features, ema_alpha, free_slots, cascade_depth,
-                       camera_matrix, predict):
+                       camera_matrix, predict, what="SortStore.frame"):
         """The host side of frame(), before anything is allocated -> (slot int32 [n], first, again, stale uint8 [n], free int32, tlwh [m,4],
         xyah [m,4], confidences [m] or None, matrix [9] or None)."""
-        what = "SortStore.frame"
         if self.feature_dim is None:
             raise ValueError("%s needs the feature rows: SortStore(capacity, feature_dim=E)" % what)
         if not APPEAR_E_MIN <= self.feature_dim <= APPEAR_E_MAX or self.feature_dim % 16:
@@ -518,6 +524,157 @@ class SortStore:
         new = host[solved + 2 * n:] if apply else np.full(m, -1, dtype=np.int32)
         return SortFrame([(r, int(r2c[r])) for r in rows], [int(r) for r in np.nonzero(r2c < 0)[0]], [int(j) for j in np.nonzero(c2r < 0)[0]],
                          [(j, int(new[j])) for j in range(m) if new[j] >= 0], [j for j in range(m) if new[j] == -2])
+
+    # ---- the frames of many sequences as one chain (busca_msframe.h, libbusca_msframe.so; busca_assign_stages over the batch)
+    def _frame_batch_checked(self, problems, ema_alpha, cascade_depth, predict):
+        """The host side of frame_batch(), before anything is allocated -> ([what _frame_checked returns, per problem], the SortFrameProblems,
+        whether the features are device tensors)."""
+        what = "SortStore.frame_batch"
+        problems = [p if isinstance(p, SortFrameProblem) else SortFrameProblem(*p) for p in problems]
+        if len(problems) > _msframe_lib.MAX_BATCH:
+            raise ValueError("%s: %d problems, one call takes %d" % (what, len(problems), _msframe_lib.MAX_BATCH))
+        checked, on_device = [], None
+        for k, p in enumerate(problems):
+            name = "%s: problem %d" % (what, k)
+            try:
+                c = self._frame_checked(p.slots, p.time_since_update, p.confirmed, p.det_tlwh, p.det_confidence, p.det_features, ema_alpha,
+                                        p.free_slots, cascade_depth, p.camera_matrix, predict, what=name)
+            except ValueError as e:
+                if name in str(e):
+                    raise
+                raise ValueError("%s: %s" % (name, e)) from None
+            if len(c[5]):                                                      # one feature table: concatenated on the host, or by one torch.cat
+                dev = torch.is_tensor(p.det_features)
+                if on_device is None:
+                    on_device = dev
+                elif on_device != dev:
+                    raise ValueError("%s: host and device det_features in one batch (the earlier problems gave %s)"
+                                     % (name, "device tensors" if on_device else "host arrays"))
+            checked.append(c)
+        if len(checked) > 1:                                                   # one launch serves them all: what two problems share, two workgroups race on
+            rows = np.concatenate([c[0] for c in checked])
+            taken = np.concatenate([rows[rows >= 0]] + [c[4] for c in checked])
+            if len(np.unique(taken)) != len(taken):
+                slots, count = np.unique(taken, return_counts=True)
+                raise ValueError("%s: the tracks and the free slots must be distinct across the whole batch (slot %d is listed twice)"
+                                 % (what, int(slots[count > 1][0])))
+        return checked, problems, bool(on_device)
+
+    def frame_batch(self, problems, max_iou_distance, matching_threshold, ema_alpha, cascade_depth=None, mc_lambda=None, predict=True, apply=True):
+        """frame() of every SortFrameProblem(slots, time_since_update, confirmed, det_tlwh, det_confidence, det_features, free_slots, camera_matrix)
+        of a list - the frames of one time step of many sequences that share this store - as ONE chain on the stream -> [SortFrame], each what
+        frame() returns for that problem alone, the states and feature rows bit for bit what the frames one after the other leave.  Whatever the
+        number of problems: one pinned upload of every small table, one float64 upload of the detection tables and the camera matrices, the
+        feature table (host arrays concatenated and uploaded once, device tensors by one torch.cat), busca_msframe_advance, busca_msframe_cost
+        (which forms the appearance entries of its tiles itself: no appearance launch, no [n, m] matrix), busca_assign_stages over the batch with
+        its `dims`, busca_msframe_apply, and ONE device->host copy of B (4 N + 2 M + 1) words, N and M the largest track and detection counts.
+        The thresholds, `ema_alpha`, `mc_lambda` and `cascade_depth` are the batch's, as the solver's stage table is; the camera matrix is the
+        problem's.  A problem with det_confidence=None has confidence 0.  The tracks and the free slots must be distinct across the whole batch
+        (ValueError, before anything is allocated).  An empty list gives []; without any detection only the advance happens and nothing is
+        copied; a problem without tracks starts a track per detection.  Raises LinAlgError (a gate or an update) and BuscaError (a solver status)
+        naming the problem, after the whole batch has been applied.  For a single sequence frame() is the shorter route."""
+        checked, problems, on_device = self._frame_batch_checked(problems, ema_alpha, cascade_depth, predict)
+        B = len(checked)
+        if B == 0:
+            return []
+        what = "SortStore.frame_batch"
+        W, E = _msframe_lib.PROBLEM_WORDS, self.feature_dim
+        depth = 1 if cascade_depth is None else int(cascade_depth)
+        n_k, m_k, f_k = ([len(c[i]) for c in checked] for i in (0, 5, 4))
+        N, M = max(n_k), max(m_k)
+        n_total, m_total, f_total = sum(n_k), sum(m_k), sum(f_k)
+        with_matrix = [k for k, c in enumerate(checked) if c[8] is not None]
+        table = np.zeros((B, W), dtype=np.int32)                               # row_begin, n_k, det_begin, m_k, free_begin, n_free_k, matrix_k
+        table[:, 1], table[:, 3], table[:, 5], table[:, 6] = n_k, m_k, f_k, -1
+        table[1:, 0:6:2] = np.cumsum(table[:-1, 1:6:2], axis=0)
+        table[with_matrix, 6] = np.arange(len(with_matrix))
+        first, again = (np.full((B, N), -1, dtype=np.int32) for _ in range(2))  # padded for the solver; the kernels read the concatenated lists
+        for k, c in enumerate(checked):
+            first[k, :n_k[k]], again[k, :n_k[k]] = c[1], c[2]
+        # one pinned upload of every small table: the 16-byte stage records first, then the int32 tables, then the `stale` bytes
+        stages = np.zeros(depth + 1, dtype=np.dtype([("plane", "<i4"), ("reserved", "<i4"), ("limit", "<f8")]))
+        stages["plane"] = [0] * depth + [1]
+        stages["limit"] = [float(matching_threshold) + 1e-5] * depth + [float(max_iou_distance) + 1e-5]
+        parts = [np.concatenate([c[0] for c in checked]), table.reshape(-1), table[:, 1:4:2].reshape(-1), first.reshape(-1), again.reshape(-1),
+                 np.concatenate([c[1] for c in checked]), np.concatenate([c[2] for c in checked]), np.concatenate([c[4] for c in checked])]
+        ints = np.concatenate(parts).astype(np.int32)
+        flags = np.zeros(-(-n_total // 4) * 4, dtype=np.uint8)
+        flags[:n_total] = np.concatenate([c[3] for c in checked])
+        up = h2d_async(np.concatenate([stages.view(np.uint8).reshape(-1), ints.view(np.uint8), flags]), self.dev)
+        at = 16 * (depth + 1)
+        d_slot, d_table, d_dims, d_first, d_again, d_first_rows, d_again_rows, d_free = up[at:at + 4 * len(ints)].view(torch.int32).split([len(p) for p in parts])
+        d_stale = up[at + 4 * len(ints):]
+        # one float64 upload: measurements, boxes, confidences (zeros where a problem gives none), the camera matrices
+        with_conf = m_total > 0 and any(c[7] is not None for c in checked)
+        cols = []
+        if m_total:
+            cols = [c[6].reshape(-1) for c in checked] + [c[5].reshape(-1) for c in checked]
+            if with_conf:
+                cols += [np.zeros(m) if c[7] is None else c[7] for m, c in zip(m_k, checked)]
+        cols += [checked[k][8] for k in with_matrix]
+        dets = small_to_dev(np.concatenate(cols), self.dev, torch.float64) if cols else None
+        d_xyah, d_tlwh = (dets[:4 * m_total], dets[4 * m_total:8 * m_total]) if m_total else (None, None)
+        d_conf = dets[8 * m_total:9 * m_total] if with_conf else None
+        d_matrices = dets[dets.numel() - 9 * len(with_matrix):] if with_matrix else None
+        self._state()
+        mlib = _msframe_lib.load()
+        where = self._where()
+        if predict and n_total:
+            _msframe_lib.check(mlib.busca_msframe_advance(self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), n_total, m_total,
+                                                          f_total, _lib.ptr(d_matrices), len(with_matrix), d_table.data_ptr(), B, N, M, *where))
+        if M == 0:
+            return [SortFrame([], list(range(n)), [], [], []) for n in n_k]
+        # the feature table: one upload, or one concatenation on the device
+        rows = [p.det_features for p, m in zip(problems, m_k) if m]
+        if on_device:
+            feats = [to_dev(r, self.dev, torch.float32) for r in rows]
+            feats = feats[0] if len(feats) == 1 else torch.cat(feats)
+        else:
+            feats = to_dev(np.concatenate([np.asarray(r, dtype=np.float32) for r in rows]), self.dev, torch.float32)
+        ctx = geometry.default_context(self.dev.index)
+        solved = B * (2 * N + M + 1)                                           # row_to_col [B,N] | col_to_row [B,M] | row_stage [B,N] | solver status [B]
+        out = torch.empty(solved + B * (2 * N + M), dtype=torch.int32, device=self.dev)      # ... | gate status [B,N] | update status [B,N] | new_slot [B,M]
+        slab = torch.empty(B, 2, N, M, dtype=torch.float64, device=self.dev)
+        base = out.data_ptr()
+        if N:
+            _msframe_lib.check(mlib.busca_msframe_cost(
+                self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr(), n_total, d_xyah.data_ptr(), d_tlwh.data_ptr(),
+                feats.data_ptr(), m_total, f_total, len(with_matrix), d_stale.data_ptr(), self.feat.data_ptr(), E, INFTY_COST,
+                (_msframe_lib.MC if mc_lambda is not None else 0) | _msframe_lib.CLAMP, 0.0 if mc_lambda is None else float(mc_lambda),
+                float(matching_threshold), float(max_iou_distance), d_first_rows.data_ptr(), d_again_rows.data_ptr(), depth, d_table.data_ptr(), B, N, M,
+                slab.data_ptr(), base + 4 * solved, *where))
+        _assign_stages_dev(ctx, slab, up[:at], d_first, d_again, d_dims, into=out)
+        if apply:
+            _msframe_lib.check(mlib.busca_msframe_apply(
+                self.mean.data_ptr(), self.cov.data_ptr(), self.capacity, d_slot.data_ptr() if n_total else None, n_total, base if N else None,
+                base + 4 * B * N, d_xyah.data_ptr(), _lib.ptr(d_conf), feats.data_ptr(), m_total, self.feat.data_ptr(), E, float(ema_alpha),
+                d_free.data_ptr() if f_total else None, f_total, len(with_matrix), d_table.data_ptr(), B, N, M, base + 4 * (solved + 2 * B * N),
+                base + 4 * (solved + B * N) if N else None, *where))
+        host = (out if apply else out[:solved + B * N]).cpu().numpy()          # the one device->host copy
+        # the words of problem k are the corner (n_k, m_k) of its blocks: the kernels write nothing else, and nothing else is read
+        r2c, c2r, stage, status = np.split(host[:solved], [B * N, B * (N + M), B * (2 * N + M)])
+        r2c, c2r, stage = r2c.reshape(B, N), c2r.reshape(B, M), stage.reshape(B, N)
+        gate = host[solved:solved + B * N].reshape(B, N)
+        flagged, new = (host[solved + B * N:solved + 2 * B * N].reshape(B, N), host[solved + 2 * B * N:].reshape(B, M)) if apply else (None, None)
+        for k, (n, m) in enumerate(zip(n_k, m_k)):                             # in the order frame() raises, problem by problem
+            name = "%s: problem %d" % (what, k)
+            if n and m:                                                        # the cost kernel writes the words of the problems that have a tile
+                _raise_flagged(gate[k, :n], name)
+            if status[k] != 0:
+                raise _lib.BuscaError("%s: the solver ran out of its loop bounds (status %d) - is a cost -inf or a limit infinite?" % (name, int(status[k])))
+            if apply and m:
+                _raise_flagged(flagged[k, :n], name + ": update")
+        frames = []
+        for k, (n, m) in enumerate(zip(n_k, m_k)):
+            if m == 0:
+                frames.append(SortFrame([], list(range(n)), [], [], []))
+                continue
+            r, c, st = r2c[k, :n], c2r[k, :m], stage[k, :n]
+            rows = [int(i) for i in np.lexsort((np.arange(n), st)) if r[i] >= 0]      # by stage, then by row: the order _match lists them in
+            started = new[k, :m] if apply else np.full(m, -1, dtype=np.int32)
+            frames.append(SortFrame([(i, int(r[i])) for i in rows], [int(i) for i in np.nonzero(r < 0)[0]], [int(j) for j in np.nonzero(c < 0)[0]],
+                                    [(j, int(started[j])) for j in range(m) if started[j] >= 0], [j for j in range(m) if started[j] == -2]))
+        return frames
 
     def features(self, slots):
         """The feature rows of the listed slots -> device float32 [n, feature_dim]; a negative entry gives the spare slot's row."""

@@ -36,6 +36,6 @@ from .ghost_motion import GhostMotion, ghost_motion_check_config  # noqa: F401
 from .kalman import (CHI2INV95, TRACKED, fuse_motion, gate_cost_matrix, gating_distance, multi_initiate, multi_predict, multi_update,  # noqa: F401
                      predicted_cost, tlwh_to_xyah)
 from .kalman_store import ByteFrame, FrameProblem, KalmanStore, RoundProblem  # noqa: F401
-from .sort_store import SortFrame, SortStore  # noqa: F401
+from .sort_store import SortFrame, SortFrameProblem, SortStore  # noqa: F401
 from .track_boxes import (center_distance, get_detection_coverage, iou_distance, is_reliable, missing_candidate_bbox, recover_with_busca,  # noqa: F401
                           remove_duplicate_stracks, warp_pos)
