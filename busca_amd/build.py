@@ -44,7 +44,7 @@ SORT_HEADERS = ["busca_sort.h", "busca_hip.h"]
 FRAME_OUT = os.path.join(HERE, "libbusca_frame.so")
 FRAME_UNITS = [("busca_frame", False)]
 FRAME_HEADERS = ["busca_frame.h", "busca_hip.h"]
-# libbusca_sframe.so (include/busca_sframe.h): the context-free library of a StrongSORT frame on resident state - predict with the camera update, the
+# libbusca_sframe.so (include/busca_sframe.h): the context-free library of a StrongSORT frame on resident state - the camera update with predict, the
 # cost slab of Tracker._match and the match vectors applied to the Kalman state and the feature rows.  Handled as the five above; it compiles the kernel
 # includes of the sort and store libraries under its own sframe_kernel, so an edit there rebuilds it too.
 SFRAME_OUT = os.path.join(HERE, "libbusca_sframe.so")

@@ -93,7 +93,7 @@ static MSFrame table_of(const int32_t* slot, const int32_t* free_slot, const int
     return b;
 }
 
-extern "C" int busca_msframe_version(void) { return 1000; }
+extern "C" int busca_msframe_version(void) { return 1001; }
 
 extern "C" const char* busca_msframe_last_error(void) { return g_err; }
 

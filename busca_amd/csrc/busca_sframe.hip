@@ -65,7 +65,7 @@ struct DeviceScope {
         if (e_ != hipSuccess) return refuse(BUSCA_SFRAME_EHIP, "%s: %s", who, hipGetErrorString(e_));                   \
     } while (0)
 
-extern "C" int busca_sframe_version(void) { return 1000; }
+extern "C" int busca_sframe_version(void) { return 1001; }
 
 extern "C" const char* busca_sframe_last_error(void) { return g_err; }
 

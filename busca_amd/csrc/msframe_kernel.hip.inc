@@ -5,8 +5,8 @@
 // one detection table, one list of free slots and a list of camera matrices, and padded [batch, 2, N, M] / [batch, N] / [batch, M] blocks for the
 // solver between the calls.
 //
-//  msframe_advance_kernel : grid (N, batch), 64 lanes.  Workgroup (x, k) with x < n_k is row x of problem k: Track.predict and, where the problem has
-//      a matrix, Track.camera_update with it.
+//  msframe_advance_kernel : grid (N, batch), 64 lanes.  Workgroup (x, k) with x < n_k is row x of problem k: where the problem has a matrix,
+//      Track.camera_update with it, and then Track.predict.
 //  msframe_cost_kernel    : grid (ceil(M / PW_TB), ceil(N / PW_TA), batch), 256 lanes.  Workgroup (x, y, k) serves tile (y, x) of problem k, if that tile
 //      lies inside (n_k, m_k).  The appearance entries of the tile come first, as the plain flavour of appear_kernel forms them: wave w owns the
 //      detections 16 w .. 16 w + 15 of the tile, lane (a, b) loads the feature row of tile row a (gathered through the slot list) and of detection

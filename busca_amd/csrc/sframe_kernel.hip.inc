@@ -3,8 +3,8 @@
 // kalman_gate_one, kalman_box_of and kalman_initiate_track of track_kernel.hip.inc, store_blend, store_div_rn and store_sqrt_rn of
 // store_kernel.hip.inc, the addressing of kalman_store_kernel.hip.inc (KStore, kstore_live) - all included by the unit before this file.
 //
-//  sframe_advance_kernel : one 64-lane workgroup per listed slot: Track.predict, a barrier, then (with a warp) Track.camera_update of the predicted
-//      mean by lane 0 - the statements of sort_camera_update_kernel on one track.
+//  sframe_advance_kernel : one 64-lane workgroup per listed slot: (with a warp) Track.camera_update of the stored mean by lane 0 - the statements of
+//      sort_camera_update_kernel on one track -, a barrier, then Track.predict.
 //  sframe_cost_kernel    : the [2, n, m] slab.  A PW_TA x PW_TB (16 x 64) tile per 256-lane workgroup, as sort_gate_cost_kernel and
 //      sort_iou_cost_kernel, which it merges: lanes 0 .. 15 stage one track each (projected mean, Cholesky factor, tlwh box - each only where the
 //      row's stage reads that plane), all lanes stage the detections, then every lane produces the four rows of one column in both planes.
@@ -20,24 +20,27 @@
 // No multiply-add contraction anywhere in this file (store_kernel.hip.inc, included last, leaves the file-scope mode at `fast`).
 #pragma clang fp contract(off)
 
-// Track.predict of the state at (pm, pc) and, with a warp, Track.camera_update of the predicted mean by lane 0.  All 64 lanes of the workgroup call it
-// (with a warp it holds a barrier).  sframe_advance_kernel and msframe_advance_kernel (msframe_kernel.hip.inc, libbusca_msframe.so) are this function
-// behind two addressings.
+// With a warp, Track.camera_update of the stored mean by lane 0, a barrier, then Track.predict of the state at (pm, pc): the order of the reference's
+// loop (deep_sort_app.py:186-189), so the prediction's process noise reads the warped height.  All 64 lanes of the workgroup call it (with a warp it
+// holds a barrier more).  sframe_advance_kernel and msframe_advance_kernel (msframe_kernel.hip.inc, libbusca_msframe.so) are this function behind two
+// addressings.
 __device__ __forceinline__ void sframe_advance_track(double* pm, double* pc, const double* __restrict__ matrix, int tid) {
+    if (matrix != nullptr) {                                       // uniform over the workgroup
+        if (tid == 0) {
+            double b[4];
+            kalman_box_of(pm, 1, b);
+            const double m00 = matrix[0], m01 = matrix[1], m02 = matrix[2], m10 = matrix[3], m11 = matrix[4], m12 = matrix[5];
+            const double x1 = (m00 * b[0] + m01 * b[1]) + m02, y1 = (m10 * b[0] + m11 * b[1]) + m12;
+            const double x2 = (m00 * b[2] + m01 * b[3]) + m02, y2 = (m10 * b[2] + m11 * b[3]) + m12;
+            const double w = x2 - x1, h = y2 - y1;
+            pm[0] = x1 + w / 2;
+            pm[1] = y1 + h / 2;
+            pm[2] = w / h;
+            pm[3] = h;
+        }
+        __syncthreads();                                           // the warped mean is what lanes 0 .. 7 read next
+    }
     sort_predict_track(pm, pc, tid);
-    if (matrix == nullptr) return;
-    __syncthreads();                                               // the predicted mean is lanes 0 .. 7's
-    if (tid != 0) return;
-    double b[4];
-    kalman_box_of(pm, 1, b);
-    const double m00 = matrix[0], m01 = matrix[1], m02 = matrix[2], m10 = matrix[3], m11 = matrix[4], m12 = matrix[5];
-    const double x1 = (m00 * b[0] + m01 * b[1]) + m02, y1 = (m10 * b[0] + m11 * b[1]) + m12;
-    const double x2 = (m00 * b[2] + m01 * b[3]) + m02, y2 = (m10 * b[2] + m11 * b[3]) + m12;
-    const double w = x2 - x1, h = y2 - y1;
-    pm[0] = x1 + w / 2;
-    pm[1] = y1 + h / 2;
-    pm[2] = w / h;
-    pm[3] = h;
 }
 
 __global__ void __launch_bounds__(64) sframe_advance_kernel(KStore k, const double* __restrict__ matrix) {

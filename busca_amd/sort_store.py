@@ -21,8 +21,8 @@ from .kalman_store import KalmanStore, _small
 
 
 # what SortStore.frame returns: the matches as (row, detection) in the order Tracker._match lists them (the cascade level by level, then the IoU
-# stage; rows index `slots`), the rows and the detections nothing matched, the tracks started as (detection, slot), and the detections that would have
-# started one but found the store full
+# stage, its unconfirmed tracks first; rows index `slots`), the rows and the detections nothing matched, the tracks started as (detection, slot),
+# and the detections that would have started one but found the store full
 SortFrame = collections.namedtuple("SortFrame", "matches unmatched_tracks unmatched_detections new_tracks overflow")
 # one frame of SortStore.frame_batch: the arguments of frame() that belong to a sequence - its tracks, its detections, its free slots, its camera matrix
 SortFrameProblem = collections.namedtuple("SortFrameProblem", "slots time_since_update confirmed det_tlwh det_confidence det_features free_slots camera_matrix",
@@ -75,6 +75,14 @@ def _match_stage_tables(time_since_update, confirmed, cascade_depth):
     return first.astype(np.int32), again.astype(np.int32)
 
 
+def _match_order(stage, first, depth):
+    """The rows of a frame in the order Tracker._match lists their matches (tracker.py:233-250): by stage - the cascade level by level, then the IoU
+    stage -, inside the IoU stage the unconfirmed tracks (first == depth) before the confirmed ones that entered it again (iou_track_candidates,
+    :239-241), and by row inside each of these."""
+    n = len(stage)
+    return np.lexsort((np.arange(n), np.asarray(first[:n]) != depth, stage))
+
+
 class SortStore:
     """The Kalman state of up to `capacity` StrongSORT tracks on the device (busca_sort_*, busca_track_kalman_initiate / _boxes):
       initiate(slots, dets, det_index)       KalmanFilter.initiate: Track.__init__'s state of a new track - also how a slot is reused
@@ -87,7 +95,7 @@ class SortStore:
       appearance_round(metric, slots, ...)   the first stage of Tracker._match: appearance.appearance_round on resident state
       iou_round(slots, det_tlwh, ...)        its IoU stage: iou_cost, the clamp and the linear assignment; one copy, of match vectors
       match(metric, slots, ...)              the whole of Tracker._match - cascade, IoU stage, merge - as one staged assignment; ONE copy whatever the depth
-      frame(slots, ...)                      a whole frame on the state and the feature rows: predict, camera update, _match, update and initiation as
+      frame(slots, ...)                      a whole frame on the state and the feature rows: camera update, predict, _match, update and initiation as
                                              ONE chain -> SortFrame; needs `feature_dim`
       frame_batch(problems, ...)             the frames of one time step of many sequences that share the store: a list of SortFrameProblem, the same
                                              chain once for all of them -> [SortFrame]
@@ -342,7 +350,7 @@ class SortStore:
         of the gate behind them - whatever the depth of the cascade; no tensor op and no upload per level.  `slots`, `track_ids`,
         `time_since_update`, `confirmed` (Track.is_confirmed()): one entry per track; `det_features` [m,E], `det_xyah` and `det_tlwh` [m,4]: one
         row per detection.  `cascade_depth`: self.max_age, or None for opt.woC.  Raises LinAlgError where appearance_round on the confirmed tracks
-        raises it.  -> (matches [(row, detection)] of the cascade and of the IoU stage in stage order, unmatched rows, unmatched detections); rows
+        raises it.  -> (matches [(row, detection)] of the cascade and of the IoU stage in _match's order (_match_order), unmatched rows, unmatched detections); rows
         index `slots`.  appearance_round + iou_round, composed as _match composes them, give the same answer with a copy per populated level."""
         slot, n = _slots_checked(slots, self.capacity, "SortStore.match")
         track_ids = list(track_ids)
@@ -380,7 +388,7 @@ class SortStore:
         if host[words - 1] != 0:
             raise _lib.BuscaError("SortStore.match: the solver ran out of its loop bounds (status %d) - is a cost -inf or a limit infinite?" % int(host[words - 1]))
         r2c, c2r, stage = host[:n], host[n:n + m], host[n + m:2 * n + m]
-        rows = [int(r) for r in np.lexsort((np.arange(n), stage)) if r2c[r] >= 0]      # by stage, then by row: the order _match lists them in
+        rows = [int(r) for r in _match_order(stage, first, depth) if r2c[r] >= 0]
         return [(r, int(r2c[r])) for r in rows], [int(r) for r in np.nonzero(r2c < 0)[0]], [int(j) for j in np.nonzero(c2r < 0)[0]]
 
     # ---- a whole frame as one chain (busca_sframe.h, libbusca_sframe.so; busca_appearance_cost, busca_assign_stages)
@@ -424,7 +432,7 @@ class SortStore:
         matrix = None
         if camera_matrix is not None:
             if not predict:
-                raise ValueError("%s: the camera update follows the prediction; with predict=False call camera_update() yourself" % what)
+                raise ValueError("%s: the camera update precedes the prediction; with predict=False call camera_update() and predict() yourself" % what)
             if torch.is_tensor(camera_matrix):
                 raise ValueError("%s takes a host 3 x 3 camera matrix" % what)
             matrix = np.asarray(camera_matrix, dtype=np.float64)
@@ -436,8 +444,9 @@ class SortStore:
 
     def frame(self, slots, time_since_update, confirmed, det_tlwh, det_confidence, det_features, max_iou_distance, matching_threshold, ema_alpha,
               free_slots=(), cascade_depth=None, mc_lambda=None, camera_matrix=None, predict=True, apply=True):
-        """One Tracker.predict / camera_update / update (adapters/StrongSORT/deep_sort/tracker.py:74-126, 197-252) on resident state as ONE chain on
-        the stream: busca_sframe_advance (Track.predict and, with `camera_matrix`, Track.camera_update), busca_appearance_cost of `det_features`
+        """One Tracker.camera_update / predict / update (adapters/StrongSORT/deep_sort/tracker.py:74-126, 197-252) on resident state as ONE chain on
+        the stream: busca_sframe_advance (with `camera_matrix`, Track.camera_update, and then Track.predict - the order of the reference's loop,
+        deep_sort_app.py:186-189: the prediction reads the warped height), busca_appearance_cost of `det_features`
         against the feature rows of the listed slots, busca_sframe_cost (both planes of the slab of match(), each row only in the planes its stage
         reads), busca_assign_stages with the stage list and row tables of match(), and - unless `apply` is false - busca_sframe_apply: Track.update of
         every matched track (the EMA feature row, track.py:244-248, then the NSA Kalman update with the detection's confidence) and
@@ -520,7 +529,7 @@ class SortStore:
         if apply:
             _raise_flagged(host[solved + n:solved + 2 * n], "SortStore.frame: update")
         r2c, c2r, stage = host[:n], host[n:n + m], host[n + m:2 * n + m]
-        rows = [int(r) for r in np.lexsort((np.arange(n), stage)) if r2c[r] >= 0]      # by stage, then by row: the order _match lists them in
+        rows = [int(r) for r in _match_order(stage, first, depth) if r2c[r] >= 0]
         new = host[solved + 2 * n:] if apply else np.full(m, -1, dtype=np.int32)
         return SortFrame([(r, int(r2c[r])) for r in rows], [int(r) for r in np.nonzero(r2c < 0)[0]], [int(j) for j in np.nonzero(c2r < 0)[0]],
                          [(j, int(new[j])) for j in range(m) if new[j] >= 0], [j for j in range(m) if new[j] == -2])
@@ -670,7 +679,7 @@ class SortStore:
                 frames.append(SortFrame([], list(range(n)), [], [], []))
                 continue
             r, c, st = r2c[k, :n], c2r[k, :m], stage[k, :n]
-            rows = [int(i) for i in np.lexsort((np.arange(n), st)) if r[i] >= 0]      # by stage, then by row: the order _match lists them in
+            rows = [int(i) for i in _match_order(st, checked[k][1], depth) if r[i] >= 0]
             started = new[k, :m] if apply else np.full(m, -1, dtype=np.int32)
             frames.append(SortFrame([(i, int(r[i])) for i in rows], [int(i) for i in np.nonzero(r < 0)[0]], [int(j) for j in np.nonzero(c < 0)[0]],
                                     [(j, int(started[j])) for j in range(m) if started[j] >= 0], [j for j in range(m) if started[j] == -2]))

@@ -48,14 +48,15 @@ extern "C" {
 #define BUSCA_MSFRAME_E_MIN 16        /* the feature widths of busca_msframe_cost: multiples of 16 in BUSCA_APPEAR_E_MIN .. BUSCA_APPEAR_E_MAX */
 #define BUSCA_MSFRAME_E_MAX 2048
 
-/* 1000 * major + minor; this header is version 1000. */
+/* 1000 * major + minor; this header is version 1001 (1001: busca_msframe_advance warps the stored
+ * mean before it predicts, as busca_sframe_advance 1001 does). */
 int busca_msframe_version(void);
 
 /* The message of the calling thread's last refused or failed call ("" when there was none).  Thread-local; valid until that thread's next call. */
 const char* busca_msframe_last_error(void);
 
-/* Track.predict of every row of every problem in place and, for the problems with matrix_k >= 0, Track.camera_update of the predicted mean with
- * matrices[matrix_k] (dev f64 [n_matrices, 9], row-major 3 x 3; NULL with n_matrices = 0).  A grid of (N, batch) 64-lane workgroups: row x of
+/* For the problems with matrix_k >= 0, Track.camera_update of the stored mean of every row with matrices[matrix_k] (dev f64 [n_matrices, 9],
+ * row-major 3 x 3; NULL with n_matrices = 0), and then Track.predict of every row of every problem in place.  A grid of (N, batch) 64-lane workgroups: row x of
  * problem k finds itself from its block index, without a table of its own and without atomics.  Bit-equal to busca_sframe_advance problem by
  * problem.  batch = 0, N = 0 or n_total = 0: returns 0 and launches nothing. */
 int busca_msframe_advance(double* mean, double* cov, int32_t S, const int32_t* slot, int32_t n_total, int32_t m_total, int32_t f_total,

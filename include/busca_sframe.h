@@ -4,7 +4,7 @@
  * skipped and touches no memory), and beside it one float32 feature row per slot (feat f32 [S + 1, E]: the track's features[-1] of
  * adapters/StrongSORT/deep_sort/track.py:85-87, 244-248).  Tracker.predict, Tracker.camera_update, Tracker._match and Tracker.update
  * (deep_sort/tracker.py:74-126, 197-252) form a chain around busca_assign_stages (busca_assign_stages.h); the three calls here are its other links:
- *   busca_sframe_advance  Track.predict and, with a warp, Track.camera_update of every listed track in one launch
+ *   busca_sframe_advance  with a warp, Track.camera_update, and then Track.predict of every listed track in one launch
  *   busca_sframe_cost     both planes of the [2, n, m] cost slab of Tracker._match in one launch: the gated appearance cost of the cascade in plane
  *                         0, the IoU cost in plane 1, each only at the rows whose stage reads it
  *   busca_sframe_apply    the solver's match vectors applied to the state: the EMA feature and the NSA Kalman update of every matched track,
@@ -39,15 +39,17 @@ extern "C" {
 
 #define BUSCA_SFRAME_MAX_DETS 2048 /* most detections of one busca_sframe_apply call (BUSCA_ASSIGN_MAX: what the solver before it takes) */
 
-/* 1000 * major + minor; this header is version 1000. */
+/* 1000 * major + minor; this header is version 1001 (1001: busca_sframe_advance warps the stored
+ * mean before it predicts, as the reference's loop does; 1000 predicted first). */
 int busca_sframe_version(void);
 
 /* The message of the calling thread's last refused or failed call ("" when there was none).  Thread-local; valid until that thread's next call. */
 const char* busca_sframe_last_error(void);
 
-/* Track.predict of every listed slot in place and, when `matrix` (dev f64 [3, 3], row-major; NULL: none) is given, Track.camera_update of the
- * predicted mean with it: a coordinate is warped as (m00 * x + m01 * y) + m02, left to right.  One 64-lane workgroup per listed slot.  Bit-equal to
- * busca_sort_predict followed by busca_sort_camera_update.  n = 0: returns 0 and launches nothing. */
+/* When `matrix` (dev f64 [3, 3], row-major; NULL: none) is given, Track.camera_update of the stored mean of every listed slot with it - a coordinate
+ * is warped as (m00 * x + m01 * y) + m02, left to right - and then Track.predict of the slot in place, which reads the warped height: the order of
+ * the reference's loop (deep_sort_app.py:186-189).  One 64-lane workgroup per listed slot.  Bit-equal to busca_sort_camera_update followed by
+ * busca_sort_predict.  n = 0: returns 0 and launches nothing. */
 int busca_sframe_advance(double* mean, double* cov, int32_t S, const int32_t* slot, int32_t n, const double* matrix, int32_t device, void* stream);
 
 /* The cost slab of Tracker._match:  out  dev f64 [2, n, m], rows the listed slots, columns the detections; it must not be `cost`.

@@ -1,10 +1,12 @@
 """A whole StrongSORT frame on resident state: libbusca_sframe.so (include/busca_sframe.h), its binding busca_amd._sframe_lib and SortStore.frame -
-predict with the camera update, both planes of the cost slab, busca_assign_stages, the EMA feature rows, the NSA update and initiation as one chain.
+the camera update and the prediction, both planes of the cost slab, busca_assign_stages, the EMA feature rows, the NSA update and initiation as one chain.
 
 The oracle is the set of calls this repository had before and pins elsewhere: SortStore.predict / camera_update / gate_cost / iou_cost / match /
 update / initiate (tests/test_sort_store.py, tests/test_assign_stages.py) and busca_store_ema_fit (tests/test_store_kernels.py), composed on a
 second store loaded alike (`_composed` below).  Every comparison is np.array_equal - match lists, new tracks, and the whole of mean, cov and feat;
-no tolerance is introduced here.  (A row whose covariance is not positive definite is NaN in both routes: asserted with np.isnan.)"""
+no tolerance is introduced here.  (A row whose covariance is not positive definite is NaN in both routes: asserted with np.isnan.)  What the
+composition itself must be - which call follows which, what the host does between them - is pinned to the reference's own tracker by
+tests/test_sort_tracker_replay.py, which found the order of camera update and prediction used here until version 1001."""
 import os
 import re
 import subprocess
@@ -55,7 +57,7 @@ def test_header_binding_and_exports_agree():
         assert not (theirs & ours), other
     assert "busca_sframe.h" not in _lib.HEADERS and "_sframe_lib" not in open(_lib.__file__.replace(".pyc", ".py")).read()
     lib = _sframe_lib.load()
-    assert lib.busca_sframe_version() == 1000 and _sframe_lib.ABI_MAJOR == 1 and lib.busca_sframe_last_error() is not None
+    assert lib.busca_sframe_version() == 1001 and _sframe_lib.ABI_MAJOR == 1 and lib.busca_sframe_last_error() is not None
 
 
 def test_refusals_and_noops_need_no_gpu():
@@ -336,12 +338,12 @@ class RowMetric:
 
 
 def _composed(st, sc, free, depth, lam, mat, ctx, predict=True, apply=True):
-    """The frame on the calls this repository had before: predict, camera_update, match with a metric over the same rows, update, initiate and
+    """The frame on the calls this repository had before: camera_update, predict (the reference's order, deep_sort_app.py:186-189), match with a metric over the same rows, update, initiate and
     busca_store_ema_fit for the rows -> what SortFrame holds, as plain lists, and the update's status words."""
     if predict:
-        st.predict(sc.slots)
         if mat is not None:
             st.camera_update(sc.slots, mat)
+        st.predict(sc.slots)
     if sc.m == 0:
         return dict(matches=[], unmatched_tracks=list(range(sc.n)), unmatched_detections=[], new_tracks=[], overflow=[], status=np.zeros(0, dtype=np.int32))
     matches, ut, ud = st.match(RowMetric(st, ctx), sc.slots, [int(s) for s in sc.slots], sc.tsu, sc.confirmed, st._det_feats, sc.xyah, sc.tlwh, MAX_IOU,
@@ -403,7 +405,7 @@ def busy():
 @pytest.mark.gpu
 @pytest.mark.parametrize("with_matrix", [False, True])
 @pytest.mark.parametrize("n", [1, 3, 65])
-def test_advance_is_predict_then_camera_update(n, with_matrix):
+def test_advance_is_camera_update_then_predict(n, with_matrix):
     from busca_amd import _sframe_lib
     mean, cov = states(5)
     k = np.arange(n) % 24
@@ -415,17 +417,20 @@ def test_advance_is_predict_then_camera_update(n, with_matrix):
     dmat = None if mat is None else _dev(mat)
     _sframe_lib.check(_sframe_lib.load().busca_sframe_advance(a.mean.data_ptr(), a.cov.data_ptr(), 80, listed.data_ptr(), n + 2,
                                                               None if dmat is None else dmat.data_ptr(), *a._where()))
-    b.predict(listed)
     if mat is not None:
         b.camera_update(listed, mat)
+    b.predict(listed)
     after = _all_of(a)
     _same(after, _all_of(b), (n, with_matrix))
     _untouched(before, after, slots, "advance")                                    # every unlisted slot and the spare one: unchanged in every bit
     assert not np.array_equal(after[0][slots], before[0][slots]) and not np.array_equal(after[1][slots], before[1][slots])
-    if mat is not None:                                                            # the warp did something: not the predicted mean
-        c = _fstore(mean[k], cov[k], slots, capacity=80)
+    if mat is not None:                                                            # the warp did something: not the predicted mean, and the
+        c, d = _fstore(mean[k], cov[k], slots, capacity=80), _fstore(mean[k], cov[k], slots, capacity=80)      # order shows in mean and covariance
         c.predict(listed)
         assert not np.array_equal(_all_of(c)[0][slots, :4], after[0][slots, :4])
+        d.predict(listed)
+        d.camera_update(listed, mat)
+        assert not np.array_equal(_all_of(d)[0][slots], after[0][slots]) and not np.array_equal(_all_of(d)[1][slots], after[1][slots])
 
 
 def _raw_cost(st, slot, xyah, tlwh, stale, cost, ld, gated, lam, first, again, depth, guard=64, canary=777.25):
@@ -638,8 +643,8 @@ def test_frame_equals_the_composed_route(ctx, n, m, depth):
     dry = _frame(a, sc, sc.free[:6], depth, 0.98, mat, apply=False)
     wet = _frame(sc.store(), sc, sc.free[:6], depth, 0.98, mat)
     assert dry[:3] == wet[:3] and dry.new_tracks == [] and dry.overflow == []
-    b.predict(sc.slots)
     b.camera_update(sc.slots, mat)
+    b.predict(sc.slots)
     _same(_all_of(a), _all_of(b), "apply=False")
     # predict=False: on states that are advanced already
     a, b = sc.store(), sc.store()
@@ -718,7 +723,8 @@ def test_not_positive_definite(ctx):
 @pytest.mark.gpu
 def test_the_scripted_scene_replays_through_frame(ctx):
     """The 12-frame scene of tests/test_sort_store.py (births, a miss, a deletion whose slot is reused, two camera updates, confidences 0 and 0.999)
-    through frame() with the host bookkeeping between frames, and through the calls of that test's replay on a second store: that test's matches
+    through frame() with the host bookkeeping between frames, and through the calls of that test's replay on a second store, with the camera update
+    before the prediction as the reference's loop has it (deep_sort_app.py:186-189): the matches of that test
     (its iou_round on all tracks - the tracks here are tentative throughout, so the IoU stage is their only one), the same states and feature rows
     after every frame."""
     frames, warps = _scene()
@@ -738,10 +744,10 @@ def test_the_scripted_scene_replays_through_frame(ctx):
         offer = free[::-1][:m]                                     # the slots the host would hand out, in the order it pops them
         got = a.frame(slots, tsu, [False] * n, det, conf, feats, 0.7, MATCH_THRESH, ALPHA, free_slots=offer, cascade_depth=30, camera_matrix=warps.get(f))
         # the replay of tests/test_sort_store.py on the second store
-        b.predict(slots)
-        if f in warps:
+        if f in warps:                                             # the reference's order: the warp, then the prediction
             b.camera_update(slots, warps[f])
             seen["camera"] += 1
+        b.predict(slots)
         want = b.iou_round(slots, det, 0.7, stale=np.array([x > 1 for x in tsu], dtype=bool))
         z = _xyah_of(det)
         if want[0]:

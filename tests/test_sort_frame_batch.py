@@ -64,7 +64,7 @@ def test_header_binding_and_exports_agree():
     assert "busca_msframe.h" not in _lib.HEADERS and "_msframe_lib" not in open(_lib.__file__.replace(".pyc", ".py")).read()
     assert builder.MSFRAME_OUT == _msframe_lib.MSFRAME_LIB_PATH and os.path.exists(builder.MSFRAME_OUT + ".flags")
     lib = _msframe_lib.load()
-    assert lib.busca_msframe_version() == 1000 and _msframe_lib.ABI_MAJOR == 1 and lib.busca_msframe_last_error() is not None
+    assert lib.busca_msframe_version() == 1001 and _msframe_lib.ABI_MAJOR == 1 and lib.busca_msframe_last_error() is not None
 
 
 def test_refusals_and_noops_need_no_gpu():
@@ -190,7 +190,7 @@ def test_python_level_checks():
             st.frame_batch([good, SortFrameProblem(**dict(other, **kw))], **KW)
     with pytest.raises(ValueError, match="problem 0.*also listed"):
         st.frame_batch([([1, 2], [1, 1], [True, False], boxes, None, feats, [2]), SortFrameProblem(**other)], **KW)      # plain tuples are taken
-    with pytest.raises(ValueError, match="problem 1.*the camera update follows the prediction"):
+    with pytest.raises(ValueError, match="problem 1.*the camera update precedes the prediction"):
         st.frame_batch([good, SortFrameProblem(**dict(other, camera_matrix=np.eye(3)))], predict=False, **KW)
     with pytest.raises(ValueError, match="problem 0.*ema_alpha"):
         st.frame_batch([good], MAX_IOU, MATCH_THRESH, None)

@@ -11,7 +11,7 @@ a camera matrix.  New tracks go into spare slots that never join, so every frame
 alike, alternating inside one loop (20 warm-up frames, host clock around a frame that ends in a stream synchronisation; p50 in microseconds):
   frame_us     SortStore.frame: two uploads, busca_sframe_advance, busca_appearance_cost, busca_sframe_cost, busca_assign_stages,
                busca_sframe_apply, ONE copy home
-  composed_us  the route of the parent commit: SortStore.predict, .camera_update, .match with a metric over the same feature rows, .update with
+  composed_us  the route of the parent commit: SortStore.camera_update, .predict, .match with a metric over the same feature rows, .update with
                the confidences, .initiate, and busca_store_ema_fit for the rows - the host between the assignment and the filter
 Both routes must return the same matches and initiations in the first frame and leave the same states and feature rows, bit for bit, after the
 last (asserted).
@@ -90,8 +90,8 @@ def main():
 
             def composed():
                 st = stores[1]
-                st.predict(slots)
                 st.camera_update(slots, WARP)
+                st.predict(slots)
                 pairs, _, ud = st.match(metric, slots, ids, tsu, confirmed, d_df, xyah, tlwh, MAX_IOU, cascade_depth=depth, mc_lambda=MC_LAMBDA)
                 st.update(slots[[i for i, _ in pairs]], xyah, [j for _, j in pairs], confidence=conf)
                 st.initiate(spare_slots[:len(ud)], xyah, ud)
