@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so, libbusca_mframe.so and libbusca_msframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so, libbusca_mframe.so, libbusca_msframe.so and libbusca_gframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -62,6 +62,13 @@ MFRAME_HEADERS = ["busca_mframe.h", "busca_frame.h", "busca_hip.h"]
 MSFRAME_OUT = os.path.join(HERE, "libbusca_msframe.so")
 MSFRAME_UNITS = [("busca_msframe", False)]
 MSFRAME_HEADERS = ["busca_msframe.h", "busca_sframe.h", "busca_appearance.h", "busca_hip.h"]
+# libbusca_gframe.so (include/busca_gframe.h): the context-free library of a GHOST frame on resident state - the warp with the motion step, the final
+# cost matrix, the threshold filter on the solver's matches and the kept matches applied to the position and feature rings.  Handled as the eight
+# above; it compiles the kernel includes of the GHOST units of libbusca_hip.so and of the store library under its own gframe_kernel, so an edit
+# there rebuilds it too.
+GFRAME_OUT = os.path.join(HERE, "libbusca_gframe.so")
+GFRAME_UNITS = [("busca_gframe", False)]
+GFRAME_HEADERS = ["busca_gframe.h", "busca_ghost.h", "busca_appearance.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -166,7 +173,7 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the nine libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the ten libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
     _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
     _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
@@ -175,6 +182,7 @@ def build(force=False, verbose=False):
     _build_lib(SFRAME_OUT, SFRAME_UNITS, SFRAME_HEADERS, force, verbose)
     _build_lib(MFRAME_OUT, MFRAME_UNITS, MFRAME_HEADERS, force, verbose)
     _build_lib(MSFRAME_OUT, MSFRAME_UNITS, MSFRAME_HEADERS, force, verbose)
+    _build_lib(GFRAME_OUT, GFRAME_UNITS, GFRAME_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

@@ -10,7 +10,8 @@
 //                           order are a permutation, so exactly one row has each rank: no atomics, no ties, the same bits every run.
 //   ghost_proxies_kernel    one workgroup per track, thread = feature (coalesced over E), rows walked in chronological order from the ring's newest
 //   ghost_thresholds_kernel one workgroup, two passes (mean, then squared deviations) per group of rows, every sum in a fixed order
-//   ghost_combine_kernel    one thread per matrix entry
+//   ghost_combine_kernel    one thread per matrix entry (ghost_combine_entry: a device function that gframe_cost_kernel, libbusca_gframe.so, applies
+//                           to each motion cost where it is produced)
 // No multiply-add contraction anywhere: every formula is written out.
 #pragma clang fp contract(off)
 
@@ -222,21 +223,28 @@ struct GhostCombineArgs {
     long long total; int m, num_active; double w_app, w_motion;
 };
 
+// One entry of busca_ghost_combine in the reference's order: the class mask, the blend with the motion cost, the threshold.  `thr`: where the
+// entry's threshold stands, or nullptr.  ghost_combine_kernel and gframe_cost_kernel (gframe_kernel.hip.inc, libbusca_gframe.so) share it.
+__device__ __forceinline__ double ghost_combine_entry(double c, bool other_class, bool blend, double motion, double w_app, double w_motion,
+                                                      const double* __restrict__ thr) {
+    if (other_class) c = __builtin_nan("");
+    if (blend) {
+        const double x = w_app * c, y = w_motion * motion;
+        c = x + y;
+    }
+    if (thr) {
+        const double t = *thr;
+        if (!(c <= t)) c = __builtin_nan("");                              // np.where(dist <= thresh, dist, nan): a NaN threshold leaves nothing
+    }
+    return c;
+}
+
 __global__ void __launch_bounds__(256) ghost_combine_kernel(GhostCombineArgs p) {
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
     if (k >= p.total) return;
     const int i = (int)(k / p.m), j = (int)(k % p.m);
-    double c = p.app[k];
-    if (p.tlabel && p.tlabel[i] != p.dlabel[j]) c = __builtin_nan("");
-    if (p.motion) {
-        const double x = p.w_app * c, y = p.w_motion * p.motion[k];
-        c = x + y;
-    }
-    if (p.thr) {
-        const double t = p.thr[i < p.num_active ? 0 : 1];
-        if (!(c <= t)) c = __builtin_nan("");                              // np.where(dist <= thresh, dist, nan): a NaN threshold leaves nothing
-    }
-    p.out[k] = c;
+    p.out[k] = ghost_combine_entry(p.app[k], p.tlabel && p.tlabel[i] != p.dlabel[j], p.motion != nullptr, p.motion ? p.motion[k] : 0.0, p.w_app,
+                                   p.w_motion, p.thr ? p.thr + (i < p.num_active ? 0 : 1) : nullptr);
 }
 
 #pragma clang fp contract(fast)

@@ -2,6 +2,7 @@
 // one launch per call:
 //
 //   store_ring_add_kernel   one workgroup per (slot, feature) pair: thread 0 does the ring bookkeeping and broadcasts the row, the threads copy the feature
+//                           (store_ring_push / store_ring_copy: device functions that gframe_kernel.hip.inc, libbusca_gframe.so, calls on one wave)
 //   store_release_kernel    one thread per listed slot
 //   store_mv_avg_kernel     one workgroup per listed track: the newest ring row, blended with the slot's moving average where it has one
 //   store_ema_fit_kernel    one workgroup per target: its features of this call in call order, the running row in LDS (E <= STORE_EMA_LDS) until the last
@@ -26,29 +27,37 @@ struct StoreRingArgs {
     int S, budget, E, m;
 };
 
+// The ring bookkeeping of busca_store_ring_add for the valid slot s, by one thread -> the ring row the new sample goes to.  `fresh` starts a new
+// track in the slot first.  store_ring_add_kernel and gframe_apply_kernel (gframe_kernel.hip.inc, libbusca_gframe.so) share it and store_ring_copy.
+__device__ __forceinline__ int store_ring_push(int* count, int* newest, unsigned char* mv_seen, int budget, int s, bool fresh) {
+    const int c = fresh ? 0 : count[s];
+    int row = 0;
+    if (c != 0) {
+        row = (int)(((long long)newest[s] + 1) % budget);                  // a row of the ring whatever `newest` holds
+        if (row < 0) row += budget;
+    }
+    if (fresh) mv_seen[s] = 0;
+    newest[s] = row;
+    count[s] = c >= budget ? budget : c + 1;
+    return row;
+}
+
+// gallery[s, row, :] = feats[j, :] by `threads` threads of which this is `tid`: the bits, whatever they encode
+__device__ __forceinline__ void store_ring_copy(float* gallery, const float* __restrict__ feats, int budget, int E, int s, int row, int j, int tid, int threads) {
+    const unsigned* src = (const unsigned*)(feats + (size_t)j * E);
+    unsigned* dst = (unsigned*)(gallery + ((size_t)s * budget + row) * E);
+    for (int e = tid; e < E; e += threads) dst[e] = src[e];
+}
+
 __global__ void __launch_bounds__(STORE_THREADS) store_ring_add_kernel(StoreRingArgs p) {
     __shared__ int ring_row;
     const int i = blockIdx.x, tid = threadIdx.x;
     const int s = p.slot[i];
     const int j = p.det_index ? p.det_index[i] : i;
     if (s < 0 || s >= p.S || j < 0 || j >= p.m) return;                   // the workgroup's: every thread leaves
-    if (tid == 0) {
-        const bool fresh = p.is_new && p.is_new[i] != 0;
-        const int c = fresh ? 0 : p.count[s];
-        int row = 0;
-        if (c != 0) {
-            row = (int)(((long long)p.newest[s] + 1) % p.budget);          // a row of the ring whatever `newest` holds
-            if (row < 0) row += p.budget;
-        }
-        if (fresh) p.mv_seen[s] = 0;
-        p.newest[s] = row;
-        p.count[s] = c >= p.budget ? p.budget : c + 1;
-        ring_row = row;
-    }
+    if (tid == 0) ring_row = store_ring_push(p.count, p.newest, p.mv_seen, p.budget, s, p.is_new && p.is_new[i] != 0);
     __syncthreads();
-    const unsigned* src = (const unsigned*)(p.feats + (size_t)j * p.E);   // the bits, whatever they encode
-    unsigned* dst = (unsigned*)(p.gallery + ((size_t)s * p.budget + ring_row) * p.E);
-    for (int e = tid; e < p.E; e += STORE_THREADS) dst[e] = src[e];
+    store_ring_copy(p.gallery, p.feats, p.budget, p.E, s, ring_row, j, tid, STORE_THREADS);
 }
 
 __global__ void __launch_bounds__(STORE_THREADS) store_release_kernel(int* count, unsigned char* mv_seen, int S, const int* slot, int k) {

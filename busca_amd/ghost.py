@@ -176,6 +176,65 @@ def _ghost_proxy_rows(ctx, g, count, newest, slot, entry, what, state=None):
     return ghost_proxies(g, mode, window, slot=slot, count=count, newest=newest, ctx=ctx)
 
 
+def _ghost_threshold_plan(cfg):
+    """tracker_cfg's two thresholds -> (act, inact, every, data_act, data_inact): the entries as given, whether 'every' rules, and which of the
+    two is computed from the frame's distances.  Raises what ghost_round raises for entries the reference cannot run."""
+    at, it = cfg.get("act_reid_thresh"), cfg.get("inact_reid_thresh")
+    every, tbd = at == "every", at == "tbd"
+    for name, v in (("act_reid_thresh", at), ("inact_reid_thresh", it)):
+        if isinstance(v, str) and v not in ("every", "tbd"):
+            raise ValueError("%s must be a number, 'every' or 'tbd', not %r" % (name, v))
+    data_act, data_inact = every or tbd, every or it == "tbd"
+    if it == "tbd" and not (every or tbd):
+        raise ValueError("inact_reid_thresh 'tbd' needs act_reid_thresh 'tbd' or 'every': the reference leaves it a string otherwise (base_tracker.py:515-531)")
+    return at, it, every, data_act, data_inact
+
+
+def _ghost_blend_plan(cfg):
+    """tracker_cfg['motion_config'] -> (motion_config, whether the motion cost is blended in, its weight alpha of combi 'sum_<alpha>')."""
+    mcfg = cfg.get("motion_config", {})
+    blend = bool(mcfg.get("apply_motion_model", False))
+    alpha = 0.0
+    if blend:
+        combi = str(mcfg.get("combi", ""))
+        if "sum" not in combi:
+            raise NotImplementedError("ghost_round: motion_config combi %r is not built; only 'sum_<alpha>'" % (combi,))
+        alpha = float(combi.split("_")[-1])
+    return mcfg, blend, alpha
+
+
+def _ghost_appearance(ctx, state, g, slot, count, newest, n, na, d, cfg):
+    """The first half of ghost_round, which GhostStore.frame runs too: the proxy and distance launches of both groups of tracks -> (app, each): the
+    device float64 [n,m] appearance matrix, tracks x detections, and whether the per-sample route ran.  `slot`: device int32 [n], ACTIVE TRACKS
+    FIRST; `d`: device float32 [m,E].  Both groups' mv_avg entries are checked before either writes its table."""
+    dev, m = g.device, d.shape[0]
+    act, inact = cfg.get("avg_act", {}), cfg.get("avg_inact", {})
+    each = inact.get("proxy") == "each_sample"
+    app = torch.empty(n, m, dtype=torch.float64, device=dev)
+    def kind(entry):                                              # what a group of tracks runs: its rows depend on nothing else
+        if each:
+            return ("samples", inact.get("num", 2)) if entry.get("do", False) else ("last",)
+        return ("proxy", entry.get("proxy", "last"), entry.get("num", "all")) if entry.get("do", False) else ("last",)
+    for entry, what in ((act, "avg_act"), (inact, "avg_inact")):  # both groups' mv_avg entries are checked before either writes its table
+        if kind(entry)[:2] == ("proxy", "mv_avg") and entry.get("num", "all") != "first":
+            _ghost_mv_avg_table(state, entry, what)
+    groups = ((0, n, inact, "avg_inact"),) if kind(act) == kind(inact) else ((0, na, act, "avg_act"), (na, n, inact, "avg_inact"))      # one launch where both groups run the same
+    if len(groups) == 2 and kind(act)[:2] == kind(inact)[:2] == ("proxy", "mv_avg") and "first" not in (act.get("num"), inact.get("num")):
+        # both groups blend, each with its own weight: one pass over all rows instead of two
+        rows = _ghost_mv_avg_rows(ctx, g, count, newest, slot, (float(act["num"]), float(inact["num"])), *_ghost_mv_avg_table(state, act, "avg_act"), num_active=na)
+        ghost_distance(rows, d, "min", out=app, ctx=ctx)
+        groups = ()
+    for lo, hi, entry, what in groups:
+        if hi == lo:
+            continue
+        if each and entry.get("do", False):                       # proxy_dist over the track's samples; both groups reduce with avg_inact['num']
+            ghost_distance(g, d, inact.get("num", 2), slot=slot[lo:hi], count=count, out=app[lo:hi], ctx=ctx)
+        else:                                                     # one vector per track (last_frame, or get_proxy), then the plain cosine distance
+            entry = {"do": False} if each else entry
+            ghost_distance(_ghost_proxy_rows(ctx, g, count, newest, slot[lo:hi], entry, what, state), d, "min", out=app[lo:hi], ctx=ctx)
+    return app, each
+
+
 def ghost_round(state, det_feats, labels=None, motion=None, cfg=None, sep=None, thresholds=None, ctx=None, det_boxes=None):
     """GHOST's association round without leaving the device: get_hungarian_each_sample / get_hungarian_with_proxy + solve_hungarian
     (adapters/GHOST/src/tracker.py:306-480) from the tracks' sample galleries and the detections' features in HBM to the matches on the host.
@@ -219,49 +278,13 @@ def ghost_round(state, det_feats, labels=None, motion=None, cfg=None, sep=None, 
         return torch.empty(m, n, dtype=torch.float64, device=dev), empty, empty
     if slot is None:
         slot = torch.arange(n, dtype=torch.int32, device=dev)
-    act, inact = cfg.get("avg_act", {}), cfg.get("avg_inact", {})
-    each = inact.get("proxy") == "each_sample"
-    app = torch.empty(n, m, dtype=torch.float64, device=dev)
-    def kind(entry):                                              # what a group of tracks runs: its rows depend on nothing else
-        if each:
-            return ("samples", inact.get("num", 2)) if entry.get("do", False) else ("last",)
-        return ("proxy", entry.get("proxy", "last"), entry.get("num", "all")) if entry.get("do", False) else ("last",)
-    for entry, what in ((act, "avg_act"), (inact, "avg_inact")):  # both groups' mv_avg entries are checked before either writes its table
-        if kind(entry)[:2] == ("proxy", "mv_avg") and entry.get("num", "all") != "first":
-            _ghost_mv_avg_table(state, entry, what)
-    groups = ((0, n, inact, "avg_inact"),) if kind(act) == kind(inact) else ((0, na, act, "avg_act"), (na, n, inact, "avg_inact"))      # one launch where both groups run the same
-    if len(groups) == 2 and kind(act)[:2] == kind(inact)[:2] == ("proxy", "mv_avg") and "first" not in (act.get("num"), inact.get("num")):
-        # both groups blend, each with its own weight: one pass over all rows instead of two
-        rows = _ghost_mv_avg_rows(ctx, g, count, newest, slot, (float(act["num"]), float(inact["num"])), *_ghost_mv_avg_table(state, act, "avg_act"), num_active=na)
-        ghost_distance(rows, d, "min", out=app, ctx=ctx)
-        groups = ()
-    for lo, hi, entry, what in groups:
-        if hi == lo:
-            continue
-        if each and entry.get("do", False):                       # proxy_dist over the track's samples; both groups reduce with avg_inact['num']
-            ghost_distance(g, d, inact.get("num", 2), slot=slot[lo:hi], count=count, out=app[lo:hi], ctx=ctx)
-        else:                                                     # one vector per track (last_frame, or get_proxy), then the plain cosine distance
-            entry = {"do": False} if each else entry
-            ghost_distance(_ghost_proxy_rows(ctx, g, count, newest, slot[lo:hi], entry, what, state), d, "min", out=app[lo:hi], ctx=ctx)
+    app, each = _ghost_appearance(ctx, state, g, slot, count, newest, n, na, d, cfg)
     tl = dl = None
     if each and labels is not None and cfg.get("nan_over_classes", True):
         tl, dl = labels
-    at, it = cfg.get("act_reid_thresh"), cfg.get("inact_reid_thresh")
-    every, tbd = at == "every", at == "tbd"
-    for name, v in (("act_reid_thresh", at), ("inact_reid_thresh", it)):
-        if isinstance(v, str) and v not in ("every", "tbd"):
-            raise ValueError("%s must be a number, 'every' or 'tbd', not %r" % (name, v))
-    data_act, data_inact = every or tbd, every or it == "tbd"
-    if it == "tbd" and not (every or tbd):
-        raise ValueError("inact_reid_thresh 'tbd' needs act_reid_thresh 'tbd' or 'every': the reference leaves it a string otherwise (base_tracker.py:515-531)")
-    mcfg = cfg.get("motion_config", {})
-    blend = bool(mcfg.get("apply_motion_model", False))
-    alpha = 0.0
+    at, it, every, data_act, data_inact = _ghost_threshold_plan(cfg)
+    mcfg, blend, alpha = _ghost_blend_plan(cfg)
     if blend:
-        combi = str(mcfg.get("combi", ""))
-        if "sum" not in combi:
-            raise NotImplementedError("ghost_round: motion_config combi %r is not built; only 'sum_<alpha>'" % (combi,))
-        alpha = float(combi.split("_")[-1])
         mstate = _ghost_get(state, "motion_state")
         if motion is None and mstate is not None and det_boxes is not None:
             ghost_motion_check_config(mcfg, cfg.get("kalman", False))

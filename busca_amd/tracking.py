@@ -12,6 +12,7 @@ each name is defined in the module of its family and re-exported here as the sam
   ghost         GHOST's proxy distances, proxies, thresholds, cost rules and round                             (busca_ghost.h)
   ghost_motion  GHOST's linear motion model                                                                    (busca_ghost_motion.h)
   ghost_gallery GHOST's feature rings and moving-average table, the state ghost_round reads                    (busca_store.h, libbusca_store.so)
+  ghost_store   GHOST's whole frame on both of those states as one chain                                       (busca_gframe.h, libbusca_gframe.so)
   ecc           camera-motion estimation for ByteTrack (u8 frames) and GHOST (float32 frames)                  (busca_hip.h, busca_ecc.h)
   crops         image crops and the host classes of the device crop pool                                       (busca_hip.h)
 Host arrays or device tensors go in; every call says in its docstring what comes back and where it lives.  There is no CPU implementation.
@@ -33,6 +34,7 @@ from .geometry import box_extents  # noqa: F401
 from .ghost import GHOST_LIMIT, ghost_check_config, ghost_cost, ghost_distance, ghost_proxies, ghost_round, ghost_thresholds  # noqa: F401
 from .ghost_gallery import GhostGallery  # noqa: F401
 from .ghost_motion import GhostMotion, ghost_motion_check_config  # noqa: F401
+from .ghost_store import GhostFrame, GhostStore  # noqa: F401
 from .kalman import (CHI2INV95, TRACKED, fuse_motion, gate_cost_matrix, gating_distance, multi_initiate, multi_predict, multi_update,  # noqa: F401
                      predicted_cost, tlwh_to_xyah)
 from .kalman_store import ByteFrame, FrameProblem, KalmanStore, RoundProblem  # noqa: F401
