@@ -1,4 +1,4 @@
-"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so, libbusca_mframe.so, libbusca_msframe.so and libbusca_gframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so, libbusca_mframe.so, libbusca_msframe.so, libbusca_gframe.so and libbusca_mgframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
 as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
@@ -69,6 +69,12 @@ MSFRAME_HEADERS = ["busca_msframe.h", "busca_sframe.h", "busca_appearance.h", "b
 GFRAME_OUT = os.path.join(HERE, "libbusca_gframe.so")
 GFRAME_UNITS = [("busca_gframe", False)]
 GFRAME_HEADERS = ["busca_gframe.h", "busca_ghost.h", "busca_appearance.h", "busca_hip.h"]
+# libbusca_mgframe.so (include/busca_mgframe.h): the context-free library of the GHOST frames of many sequences on one store - the ragged batched
+# forms of the four calls of libbusca_gframe.so and of busca_ghost_distance / busca_ghost_thresholds.  Handled as the nine above; it compiles
+# gframe_kernel, ghost_kernel and the kernel includes below them under its own mgframe_kernel, so an edit there rebuilds it too.
+MGFRAME_OUT = os.path.join(HERE, "libbusca_mgframe.so")
+MGFRAME_UNITS = [("busca_mgframe", False)]
+MGFRAME_HEADERS = ["busca_mgframe.h", "busca_gframe.h", "busca_ghost.h", "busca_appearance.h", "busca_hip.h"]
 
 
 def _requested_flags():
@@ -173,7 +179,7 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the ten libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    """(Re)build what is stale of the eleven libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
     _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
     _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
     _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
@@ -183,6 +189,7 @@ def build(force=False, verbose=False):
     _build_lib(MFRAME_OUT, MFRAME_UNITS, MFRAME_HEADERS, force, verbose)
     _build_lib(MSFRAME_OUT, MSFRAME_UNITS, MSFRAME_HEADERS, force, verbose)
     _build_lib(GFRAME_OUT, GFRAME_UNITS, GFRAME_HEADERS, force, verbose)
+    _build_lib(MGFRAME_OUT, MGFRAME_UNITS, MGFRAME_HEADERS, force, verbose)
     return _build_lib(OUT, UNITS, HEADERS, force, verbose)
 
 

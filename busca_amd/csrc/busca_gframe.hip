@@ -113,7 +113,9 @@ extern "C" int busca_gframe_cost(const double* app, const double* pos, const dou
     GFrameCost a;
     a.app = app, a.pos = pos, a.boxes = det_boxes, a.tlabel = (const int*)track_label, a.dlabel = (const int*)det_label, a.thr = thr, a.out = out;
     a.w_app = 1.0 - alpha, a.w_motion = alpha;                    // as busca_ghost_combine forms them
-    a.n = n, a.m = m, a.num_active = num_active;
+    const int na = num_active < 0 ? 0 : num_active > n ? n : num_active;      // for a row i < n, i < num_active is i < na
+    a.rows = GFrameRows{na, n - na, 0, na, na};                   // row i of the matrix is row i of pos and track_label
+    a.m = m, a.ld = m;
     GFRAME_LAUNCH(who, device, gframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, a);
     return 0;
 }
@@ -138,7 +140,7 @@ extern "C" int busca_gframe_keep(double* cost, int32_t n, int32_t m, int32_t lo,
     GFrameKeep a;
     a.cost = cost, a.row_to_col = (const int*)row_to_col, a.col_to_row = (const int*)col_to_row, a.thr = thr;
     a.track_det = (int*)track_det, a.det_track = (int*)det_track;
-    a.n = n, a.m = m, a.lo = lo, a.hi = hi, a.num_active = num_active, a.merge = merge != 0, a.mask_from = mask_from;
+    a.m = m, a.ld = m, a.lo = lo, a.hi = hi, a.num_active = num_active, a.merge = merge != 0, a.mask_from = mask_from, a.mask_to = n;
     const int threads = hi - lo > m ? hi - lo : m;
     GFRAME_LAUNCH(who, device, gframe_keep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), stream, a);
     return 0;
@@ -175,7 +177,8 @@ extern "C" int busca_gframe_apply(double* hist, int32_t* frames, int32_t* m_coun
     f.gallery = gallery, f.g_count = (int*)g_count, f.g_newest = (int*)g_newest, f.mv_seen = mv_seen;
     f.slot = (const int*)slot, f.track_det = (const int*)track_det, f.det_track = (const int*)det_track;
     f.det_feat = det_feat, f.det_boxes = det_boxes, f.may_start = may_start, f.free_slot = (const int*)free_slot, f.det_slot = (int*)det_slot;
-    f.n = n, f.m = m, f.budget = budget, f.E = E, f.frame = frame, f.n_free = n_free;
-    GFRAME_LAUNCH(who, device, gframe_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, f);
+    f.rows = GFrameRows{n, 0, 0, 0, n};                           // row i of the matrix is slot[i]
+    f.m = m, f.budget = budget, f.E = E, f.frame = frame, f.n_free = n_free;
+    GFRAME_LAUNCH(who, device, gframe_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, f, (int)n);
     return 0;
 }

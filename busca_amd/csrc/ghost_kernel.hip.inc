@@ -10,12 +10,13 @@
 //                           order are a permutation, so exactly one row has each rank: no atomics, no ties, the same bits every run.
 //   ghost_proxies_kernel    one workgroup per track, thread = feature (coalesced over E), rows walked in chronological order from the ring's newest
 //   ghost_thresholds_kernel one workgroup, two passes (mean, then squared deviations) per group of rows, every sum in a fixed order
+//   (the bodies of the first and the third are device functions of ghost_body.hip.inc, which mgframe_kernel.hip.inc, libbusca_mgframe.so, calls too)
 //   ghost_combine_kernel    one thread per matrix entry (ghost_combine_entry: a device function that gframe_cost_kernel, libbusca_gframe.so, applies
 //                           to each motion cost where it is produced)
 // No multiply-add contraction anywhere: every formula is written out.
 #pragma clang fp contract(off)
 
-#define GHOST_SEL_CHUNK 8       // rows a lane ranks at a time: one LDS read of row j serves this many comparisons
+#include "ghost_body.hip.inc"   // ghost_distance_entry, ghost_block_sum and ghost_thresholds_groups: the bodies, shared with mgframe_kernel.hip.inc
 
 struct GhostDistArgs {
     const float* gallery; const int* slot; const int* count; const float* dets; double* out;
@@ -33,77 +34,8 @@ __global__ void __launch_bounds__(64 * APPEAR_WAVES) ghost_distance_kernel(Ghost
     const int s = p.slot ? p.slot[ti] : ti;
     int cnt = s < 0 ? 0 : (p.count ? p.count[s] : p.budget);
     cnt = cnt < 0 ? 0 : cnt > p.budget ? p.budget : cnt;
-    const double inf = __builtin_huge_val();
-    double mn = inf, mx = -inf, sum = 0.0, nb = 0.0;
-    ap_f64x4 dot, ga, gb;
     const float* base = p.gallery + (size_t)(s < 0 ? 0 : s) * p.budget * p.E;
-    for (int t0 = 0; t0 < cnt; t0 += 16) {                                // the loop of appear_kernel<true>, rows beyond the count never loaded
-        const float* arow = t0 + a < cnt ? base + (size_t)(t0 + a) * p.E : nullptr;
-        if (t0 == 0) {
-            appear_tile<true>(arow, brow, p.E, b, dot, ga, gb);
-            nb = __shfl(appear_diag(gb, a), a + 16 * (a & 3));
-        } else {
-            appear_tile<false>(arow, brow, p.E, b, dot, ga, gb);
-        }
-        const double da = appear_diag(ga, a);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = b + 4 * r;
-            const double na = __shfl(da, row + 16 * b);
-            const double c = appear_dist(dot[r], na, nb, 0);
-            if (t0 + row < cnt) {
-                mn = appear_fold(mn, c, BUSCA_APPEAR_MIN);
-                mx = appear_fold(mx, c, BUSCA_APPEAR_MAX);
-                sum = appear_fold(sum, c, BUSCA_APPEAR_MEAN);
-                if (MEDIAN) ghost_lds[(size_t)(t0 + row) * APPEAR_TILE_M + col] = c;
-            }
-        }
-    }
-    mn = appear_fold(mn, __shfl_xor(mn, 16), BUSCA_APPEAR_MIN);
-    mn = appear_fold(mn, __shfl_xor(mn, 32), BUSCA_APPEAR_MIN);
-    mx = appear_fold(mx, __shfl_xor(mx, 16), BUSCA_APPEAR_MAX);
-    mx = appear_fold(mx, __shfl_xor(mx, 32), BUSCA_APPEAR_MAX);
-    sum = appear_fold(sum, __shfl_xor(sum, 16), BUSCA_APPEAR_MEAN);
-    sum = appear_fold(sum, __shfl_xor(sum, 32), BUSCA_APPEAR_MEAN);
-    double res;
-    if (cnt == 0) res = inf;
-    else if (p.reduce == BUSCA_GHOST_MIN) res = mn;
-    else if (p.reduce == BUSCA_GHOST_MAX) res = mx;
-    else if (p.reduce == BUSCA_GHOST_MEAN) res = sum / (double)cnt;
-    else res = (mx + mn) / 2.0;                                           // MIDRANGE; a NaN among the distances is in both
-    if constexpr (MEDIAN) {
-        double* sel = ghost_lds + (size_t)p.budget * APPEAR_TILE_M;       // [2][64]: the rows of rank (cnt - 1) / 2 and cnt / 2
-        __syncthreads();                                                   // cnt is the workgroup's: every wave takes the same path
-        if (cnt > 0 && mn == mn) {                                        // no NaN in this column (mn keeps one): the order is total
-            const int klo = (cnt - 1) >> 1, khi = cnt >> 1;
-            const double* v = ghost_lds + col;
-            for (int i0 = b; i0 < cnt; i0 += 4 * GHOST_SEL_CHUNK) {
-                double vi[GHOST_SEL_CHUNK];
-                int rank[GHOST_SEL_CHUNK];
-#pragma unroll
-                for (int u = 0; u < GHOST_SEL_CHUNK; ++u) {
-                    const int i = i0 + 4 * u;
-                    vi[u] = i < cnt ? v[(size_t)i * APPEAR_TILE_M] : inf;
-                    rank[u] = 0;
-                }
-                for (int jr = 0; jr < cnt; ++jr) {
-                    const double vj = v[(size_t)jr * APPEAR_TILE_M];
-#pragma unroll
-                    for (int u = 0; u < GHOST_SEL_CHUNK; ++u)
-                        rank[u] += (vj < vi[u] || (vj == vi[u] && jr < i0 + 4 * u)) ? 1 : 0;
-                }
-#pragma unroll
-                for (int u = 0; u < GHOST_SEL_CHUNK; ++u) {
-                    if (i0 + 4 * u < cnt) {
-                        if (rank[u] == klo) sel[col] = vi[u];
-                        if (rank[u] == khi) sel[APPEAR_TILE_M + col] = vi[u];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (cnt > 0) res = mn != mn ? mn : (cnt & 1) ? sel[col] : (sel[col] + sel[APPEAR_TILE_M + col]) / 2.0;
-    }
+    const double res = ghost_distance_entry<MEDIAN>(base, cnt, p.budget, brow, p.E, p.reduce, ghost_lds, col, a, b);
     if (b == 0 && j < p.m) p.out[(size_t)ti * p.m + j] = res;
 }
 
@@ -185,36 +117,9 @@ __global__ void __launch_bounds__(GHOST_PROXY_THREADS) ghost_proxies_kernel(Ghos
 }
 
 // ---- thresholds --------------------------------------------------------------------------------------------------------------------
-#define GHOST_THR_THREADS 256
-
-// the sum of f(x[k]) over k = 0 .. len-1: thread t adds k = t, t + 256, ... in ascending order, the 64 lanes of a wave are added by xor-shuffles
-// (offsets 32, 16, 8, 4, 2, 1), the four waves as (w0 + w1) + (w2 + w3).  Every thread returns the total.
-template <bool SQDEV>
-__device__ __forceinline__ double ghost_block_sum(const double* x, long long len, double mean, double* part) {
-    double acc = 0.0;
-    for (long long k = threadIdx.x; k < len; k += GHOST_THR_THREADS) {
-        const double v = x[k];
-        if (SQDEV) { const double d = v - mean; acc = acc + d * d; }
-        else acc = acc + v;
-    }
-    for (int o = 32; o >= 1; o >>= 1) acc = acc + __shfl_xor(acc, o);
-    __syncthreads();                                                       // the previous sum's readers are done with `part`
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 __global__ void __launch_bounds__(GHOST_THR_THREADS) ghost_thresholds_kernel(const double* cost, long long len_act, long long len_inact, double k_act, double k_inact, double* thr) {
     __shared__ double part[GHOST_THR_THREADS / 64];
-    for (int g = 0; g < 2; ++g) {
-        const double* x = g == 0 ? cost : cost + len_act;
-        const long long len = g == 0 ? len_act : len_inact;
-        if (len == 0) continue;                                           // no row of this kind: its threshold stays what it was
-        const double mean = ghost_block_sum<false>(x, len, 0.0, part) / (double)len;
-        const double var = ghost_block_sum<true>(x, len, mean, part) / (double)len;
-        const double kstd = (g == 0 ? k_act : k_inact) * sqrt(var);
-        if (threadIdx.x == 0) thr[g] = mean - kstd;
-    }
+    ghost_thresholds_groups<false>(cost, len_act, cost + len_act, len_inact, 0, 0, k_act, k_inact, 3, thr, part);
 }
 
 // ---- mask, blend, threshold ------------------------------------------------------------------------------------------------------

@@ -203,14 +203,25 @@ def _ghost_blend_plan(cfg):
     return mcfg, blend, alpha
 
 
-def _ghost_appearance(ctx, state, g, slot, count, newest, n, na, d, cfg):
+def _ghost_appearance(ctx, state, g, slot, count, newest, n, na, d, cfg, distance=None):
     """The first half of ghost_round, which GhostStore.frame runs too: the proxy and distance launches of both groups of tracks -> (app, each): the
     device float64 [n,m] appearance matrix, tracks x detections, and whether the per-sample route ran.  `slot`: device int32 [n], ACTIVE TRACKS
-    FIRST; `d`: device float32 [m,E].  Both groups' mv_avg entries are checked before either writes its table."""
-    dev, m = g.device, d.shape[0]
+    FIRST; `d`: device float32 [m,E].  Both groups' mv_avg entries are checked before either writes its table.
+    `distance(rows, reduce, lo, hi)`: what receives the distance launch of the tracks lo .. hi - 1 - `rows` their [hi - lo, E] proxy vectors, or None:
+    their samples in the gallery, reduced with `reduce` - in place of busca_ghost_distance into `app` (which is then None): GhostStore.frame_batch
+    writes the diagonal blocks of a batch with it."""
+    dev = g.device
     act, inact = cfg.get("avg_act", {}), cfg.get("avg_inact", {})
     each = inact.get("proxy") == "each_sample"
-    app = torch.empty(n, m, dtype=torch.float64, device=dev)
+    app = None
+    if distance is None:
+        app = torch.empty(n, d.shape[0], dtype=torch.float64, device=dev)
+
+        def distance(rows, reduce, lo, hi):
+            if rows is None:
+                ghost_distance(g, d, reduce, slot=slot[lo:hi], count=count, out=app[lo:hi], ctx=ctx)
+            else:
+                ghost_distance(rows, d, reduce, out=app[lo:hi], ctx=ctx)
     def kind(entry):                                              # what a group of tracks runs: its rows depend on nothing else
         if each:
             return ("samples", inact.get("num", 2)) if entry.get("do", False) else ("last",)
@@ -222,16 +233,16 @@ def _ghost_appearance(ctx, state, g, slot, count, newest, n, na, d, cfg):
     if len(groups) == 2 and kind(act)[:2] == kind(inact)[:2] == ("proxy", "mv_avg") and "first" not in (act.get("num"), inact.get("num")):
         # both groups blend, each with its own weight: one pass over all rows instead of two
         rows = _ghost_mv_avg_rows(ctx, g, count, newest, slot, (float(act["num"]), float(inact["num"])), *_ghost_mv_avg_table(state, act, "avg_act"), num_active=na)
-        ghost_distance(rows, d, "min", out=app, ctx=ctx)
+        distance(rows, "min", 0, n)
         groups = ()
     for lo, hi, entry, what in groups:
         if hi == lo:
             continue
         if each and entry.get("do", False):                       # proxy_dist over the track's samples; both groups reduce with avg_inact['num']
-            ghost_distance(g, d, inact.get("num", 2), slot=slot[lo:hi], count=count, out=app[lo:hi], ctx=ctx)
+            distance(None, inact.get("num", 2), lo, hi)
         else:                                                     # one vector per track (last_frame, or get_proxy), then the plain cosine distance
             entry = {"do": False} if each else entry
-            ghost_distance(_ghost_proxy_rows(ctx, g, count, newest, slot[lo:hi], entry, what, state), d, "min", out=app[lo:hi], ctx=ctx)
+            distance(_ghost_proxy_rows(ctx, g, count, newest, slot[lo:hi], entry, what, state), "min", lo, hi)
     return app, each
 
 

@@ -8,9 +8,9 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _gframe_lib, _lib, geometry
+from . import _gframe_lib, _lib, _mgframe_lib, geometry
 from ._xfer import h2d_async, stream_of, to_dev
-from .ghost import (GHOST_LIMIT, _GHOST_PROXY, _ghost_appearance, _ghost_blend_plan, _ghost_mv_avg_table, _ghost_threshold_plan, ghost_check_config,
+from .ghost import (GHOST_LIMIT, _GHOST_PROXY, _GHOST_REDUCE, _ghost_appearance, _ghost_blend_plan, _ghost_mv_avg_table, _ghost_threshold_plan, ghost_check_config,
                     ghost_thresholds)
 from .ghost_gallery import GhostGallery
 from .ghost_motion import GhostMotion, _slots_checked, ghost_motion_check_config
@@ -44,9 +44,8 @@ class GhostStore:
         self.motion = GhostMotion(capacity, history, box_dtype=box_dtype, ctx=self.ctx)
         self.capacity, self.budget, self.E, self.history = self.gallery.capacity, self.gallery.budget, self.gallery.E, self.motion.history
 
-    def _frame_checked(self, active, inactive, idle, free_slots, det_feats, det_boxes, det_conf, labels, warp, thresholds, cfg):
+    def _frame_checked(self, active, inactive, idle, free_slots, det_feats, det_boxes, det_conf, labels, warp, thresholds, cfg, what="GhostStore.frame"):
         """The host side of frame(), before anything is allocated, enqueued or written -> the plan as a dict."""
-        what = "GhostStore.frame"
         cfg = ghost_check_config(dict(cfg or {}))
         mcfg, blend, alpha = _ghost_blend_plan(cfg)
         ghost_motion_check_config(mcfg, cfg.get("kalman", False))
@@ -286,3 +285,268 @@ class GhostStore:
         if cost is not None:
             dist = [cost[:na].T, cost[na:].T if na > 0 else None] if sep else cost.T
         return GhostFrame(matches, new, overflow, [i for i in range(na) if track_det[i] < 0], [i for i in range(na, n) if track_det[i] < 0], thr, dist)
+
+    # ---- the frames of many sequences as one chain (busca_mgframe.h, libbusca_mgframe.so; busca_linear_assignment over the batch)
+    @staticmethod
+    def all_warped_after(problem, frame):
+        """What a sequence carries to its next GhostFrameProblem.all_warped: every stored row has been warped - this step had a warp, or the
+        sequence came in all warped - and no detection was added since (GhostMotion.all_warped of a tracker of its own)."""
+        return bool((problem.warp is not None or problem.all_warped) and not (frame.matches or frame.new))
+
+    def _frame_batch_checked(self, problems, cfg):
+        """The host side of frame_batch(), before anything is allocated -> ([the plan of _frame_checked, per problem], the GhostFrameProblems, whether
+        the features are device tensors)."""
+        what = "GhostStore.frame_batch"
+        problems = [p if isinstance(p, GhostFrameProblem) else GhostFrameProblem(*p) for p in problems]
+        if len(problems) > _mgframe_lib.MAX_BATCH:
+            raise ValueError("%s: %d problems, one call takes %d" % (what, len(problems), _mgframe_lib.MAX_BATCH))
+        plans, on_device = [], None
+        for k, p in enumerate(problems):
+            name = "%s: problem %d" % (what, k)
+            try:
+                c = self._frame_checked(p.active, p.inactive, p.idle, p.free_slots, p.det_feats, p.det_boxes, p.det_conf, p.labels, p.warp, None, cfg,
+                                        what=name)
+                if not -2 ** 31 <= int(p.frame) < 2 ** 31:
+                    raise ValueError("%s: frame %r is no int32" % (name, p.frame))
+            except (ValueError, NotImplementedError) as e:
+                if name in str(e):
+                    raise
+                raise type(e)("%s: %s" % (name, e)) from None
+            if c["m"]:                                             # one feature table: concatenated on the host, or by one torch.cat
+                dev = torch.is_tensor(p.det_feats)
+                if on_device is None:
+                    on_device = dev
+                elif on_device != dev:
+                    raise ValueError("%s: host and device det_feats in one batch (the earlier problems gave %s)"
+                                     % (name, "device tensors" if on_device else "host arrays"))
+            plans.append(c)
+        if len(plans) > 1:                                         # one launch serves them all: what two problems share, two workgroups race on
+            taken = np.concatenate([c["listed"] for c in plans] + [c["free"] for c in plans])
+            if len(np.unique(taken)) != len(taken):
+                slots, count = np.unique(taken, return_counts=True)
+                raise ValueError("%s: the tracks and the free slots must be distinct across the whole batch (slot %d is listed twice)"
+                                 % (what, int(slots[count > 1][0])))
+        if plans and plans[0]["each"]:                             # what busca_mgframe_distance would refuse, before anything is written
+            inact = plans[0]["cfg"].get("avg_inact", {})
+            reduce = inact.get("num", 2)
+            reduce = reduce.lower() if isinstance(reduce, str) else reduce
+            if reduce not in _GHOST_REDUCE:
+                raise ValueError("%s: avg_inact['num'] must be 'min', 'mean', 'max', 'midrange', 'median' or 1 .. 5, not %r" % (what, reduce))
+            if _GHOST_REDUCE[reduce] == _lib.GHOST_MEDIAN and self.budget > _mgframe_lib.MEDIAN_BUDGET_MAX:
+                raise ValueError("%s: the median takes a budget of at most %d, not %d" % (what, _mgframe_lib.MEDIAN_BUDGET_MAX, self.budget))
+        if plans and plans[0]["sep"]:
+            rows = max(c["na"] for c in plans) + max(c["n"] - c["na"] for c in plans)
+            if rows > _lib.ASSIGN_MAX:
+                raise ValueError("%s: with assign_separately the slab has %d rows (the most active plus the most inactive tracks of a problem), the "
+                                 "device solver takes at most %d" % (what, rows, _lib.ASSIGN_MAX))
+        return plans, problems, bool(on_device)
+
+    def frame_batch(self, problems, cfg, apply=True):
+        """frame() of every GhostFrameProblem(active, inactive, det_feats, det_boxes, frame, det_conf, idle, free_slots, labels, warp, all_warped) of a
+        list - the frames of one time step of many sequences that share this store - as ONE chain on torch's current stream -> [GhostFrame], each
+        what frame() returns for that problem on a store loaded alike whose motion.all_warped was the problem's `all_warped`; both rings are bit for
+        bit what the frames one after the other leave.  `cfg` is the batch's.  Whatever the number of problems: one pinned upload of every small table
+        (problem table, slots, free slots, labels, may_start, host warps, fixed thresholds, both `dims` tables), one float64 upload of all boxes,
+        one concatenation each where the features or the warps are device tensors, busca_mgframe_advance, the proxy launches of frame() on the whole
+        slot list (ordered group-wise: every problem's active tracks, then every problem's inactive ones, then the idle ones), busca_mgframe_distance
+        into the padded [B, R, M] slab, with data-driven thresholds the class mask and busca_mgframe_thresholds, busca_mgframe_cost, ONE batched
+        busca_linear_assignment with its `dims` (two with assign_separately, the second on the inactive rows, which start at the same slab row in
+        every problem), busca_mgframe_keep (twice with assign_separately), busca_mgframe_apply and ONE device->host copy:
+        [thr per problem, when computed on the device] | track_det | det_track | det_slot | solver status words.
+        Every check of frame() runs per problem and names it; the tracks and the free slots must be distinct across the whole batch, the features all
+        host arrays or all device tensors, and the slab within the solver's limit (ValueError, before anything is allocated, uploaded or written).
+        Every quirk frame() documents is kept per problem: a problem without detections is warped only, one without active and in-patience
+        inactive tracks starts a track per detection and is not stepped.
+        GhostMotion.all_warped is one flag for the whole store, and in the reference it belongs to one sequence: a problem carries its own
+        `all_warped` (its step's differences are float32 when the boxes are, when it has a warp, or when it says so), this call does not read
+        motion.all_warped and leaves it False, and all_warped_after(problem, frame) is what the caller carries to the sequence's next step.
+        An empty list gives [].  Raises BuscaError on a solver status naming the problem (the state update has been enqueued by then).  For a single
+        sequence frame() is the shorter route."""
+        plans, problems, on_device = self._frame_batch_checked(problems, cfg)
+        B = len(plans)
+        if B == 0:
+            return []
+        what = "GhostStore.frame_batch"
+        first = plans[0]                                           # what the cfg decides is the batch's
+        sep, blend, each = first["sep"], first["blend"], first["each"]
+        data = first["data_act"] or first["data_inact"]
+        g, mo, dev = self.gallery, self.motion, self.dev
+        mlib = _mgframe_lib.load()
+        where = (dev.index, stream_of(dev))
+        # ---- the problem table.  A problem without detections is warped only: its tracks are listed as idle rows; the others keep their groups
+        m_k = [c["m"] for c in plans]
+        na_k = [c["na"] if c["m"] else 0 for c in plans]
+        ni_k = [c["n"] - c["na"] if c["m"] else 0 for c in plans]
+        nidle_k = [len(c["listed"]) - na - ni for c, na, ni in zip(plans, na_k, ni_k)]
+        f_k = [len(c["free"]) for c in plans]
+        round_k = [na + ni > 0 and m > 0 for na, ni, m in zip(na_k, ni_k, m_k)]
+        A, I, D = sum(na_k), sum(ni_k), sum(nidle_k)
+        n_total, m_total, f_total = A + I + D, sum(m_k), sum(f_k)
+        N, M, L = max(na + ni for na, ni in zip(na_k, ni_k)), max(m_k), max(len(c["listed"]) for c in plans)
+        NA = max(na_k)
+        R, inact_row = (NA + max(ni_k), NA) if sep else (N, -1)
+        host_warps = [k for k, c in enumerate(plans) if isinstance(c["warp"], np.ndarray)]
+        dev_warps = [k for k, c in enumerate(plans) if torch.is_tensor(c["warp"])]
+        W = _mgframe_lib.PROBLEM_WORDS
+        table = np.zeros((B, W), dtype=np.int32)
+        table[:, 1], table[:, 3], table[:, 5], table[:, 7], table[:, 9], table[:, 10] = na_k, ni_k, nidle_k, m_k, f_k, -1
+        table[:, 0] = np.cumsum([0] + na_k[:-1])
+        table[:, 2] = A + np.cumsum([0] + ni_k[:-1])
+        table[:, 4] = A + I + np.cumsum([0] + nidle_k[:-1])
+        table[:, 6] = np.cumsum([0] + m_k[:-1])
+        table[:, 8] = np.cumsum([0] + f_k[:-1])
+        table[host_warps, 10] = np.arange(len(host_warps))
+        table[dev_warps, 10] = len(host_warps) + np.arange(len(dev_warps))
+        table[:, 11] = [int(p.frame) for p in problems]
+        table[:, 12] = [(_mgframe_lib.DIFF32 if mo.box32 or c["warp"] is not None or p.all_warped else 0) | (_mgframe_lib.STEP if blend and r else 0)
+                        for c, p, r in zip(plans, problems, round_k)]
+        listed = [np.concatenate([c["listed"][:na] for c, na in zip(plans, na_k)]),
+                  np.concatenate([c["listed"][na:na + ni] for c, na, ni in zip(plans, na_k, ni_k)]),
+                  np.concatenate([c["listed"][na + ni:] for c, na, ni in zip(plans, na_k, ni_k)])]
+        with_labels = each and any(c["tl"] is not None and r for c, r in zip(plans, round_k))
+        tl = dl = np.zeros(0, dtype=np.int32)
+        if with_labels:                                            # a problem without labels has one class: nothing of it is masked
+            tl = np.concatenate([c["tl"][:na] if c["tl"] is not None and r else np.zeros(na, np.int32) for c, na, r in zip(plans, na_k, round_k)]
+                                + [c["tl"][na:] if c["tl"] is not None and r else np.zeros(ni, np.int32) for c, na, ni, r in zip(plans, na_k, ni_k, round_k)])
+            dl = np.concatenate([c["dl"] if c["tl"] is not None and r else np.zeros(m, np.int32) for c, m, r in zip(plans, m_k, round_k)])
+        may = []
+        for c, na, ni in zip(plans, na_k, ni_k):
+            if na + ni == 0 or c["conf"] is None:
+                may.append(np.ones(c["m"], dtype=np.uint8))
+            else:
+                may.append((c["conf"] > c["new_track_conf"]).astype(np.uint8))
+        dims1 = np.stack([na_k if sep else [na + ni for na, ni in zip(na_k, ni_k)], m_k], axis=1)
+        dims2 = np.stack([[ni if na else 0 for na, ni in zip(na_k, ni_k)], m_k], axis=1)
+        # ---- one pinned upload: float64 thresholds [B, 2], float32 host warps, the int32 tables, the may_start bytes
+        fixed = np.tile(first["fixed"], B)
+        warps = np.concatenate([plans[k]["warp"] for k in host_warps]) if host_warps else np.zeros(0, dtype=np.float32)
+        parts = [table.reshape(-1), listed[0], listed[1], listed[2], np.concatenate([c["free"] for c in plans]), tl, dl, dims1.reshape(-1),
+                 dims2.reshape(-1)]
+        ints = np.concatenate(parts).astype(np.int32)
+        up = h2d_async(np.concatenate([fixed.view(np.uint8), warps.view(np.uint8), ints.view(np.uint8), np.concatenate(may)]), dev)
+        at = 16 * B
+        d_fixed = up[:at].view(torch.float64)
+        d_warps = up[at:at + 4 * len(warps)].view(torch.float32) if host_warps else None
+        at += 4 * len(warps)
+        d_table, d_act, d_inact, d_idle, d_free, d_tl, d_dl, d_dims1, d_dims2 = up[at:at + 4 * len(ints)].view(torch.int32).split([len(x) for x in parts])
+        d_listed = up[at + 4 * W * B:at + 4 * (W * B + n_total)].view(torch.int32)
+        d_may = up[at + 4 * len(ints):]
+        if dev_warps:                                              # one concatenation: the uploaded host warps, then the device ones
+            d_warps = torch.cat(([d_warps] if host_warps else []) + [plans[k]["warp"].reshape(6) for k in dev_warps])
+        n_warps = len(host_warps) + len(dev_warps)
+        mo.all_warped = False                                      # a sequence's flag travels with its problems (all_warped_after)
+        rings = (mo.hist.data_ptr(), mo.frames.data_ptr(), mo.count.data_ptr(), mo.newest.data_ptr(), mo.pos.data_ptr(), mo.vel.data_ptr())
+        tail = (self.capacity, d_listed.data_ptr() if n_total else None, n_total, m_total, f_total, n_warps, d_table.data_ptr(), B, N, M, L, R, inact_row)
+        stepped = blend and any(round_k)
+        pos = None
+        if n_total and (stepped or n_warps):
+            pos = torch.empty(n_total, 4, dtype=torch.float64, device=dev)
+            _mgframe_lib.check(mlib.busca_mgframe_advance(*rings, self.capacity, self.history, d_listed.data_ptr(), n_total, m_total, f_total,
+                                                          _lib.ptr(d_warps), n_warps, d_table.data_ptr(), B, N, M, L, R, inact_row, first["last_n"],
+                                                          pos.data_ptr(), *where))
+        if M == 0:
+            return [_no_frame(c["na"], c["n"] - c["na"]) for c in plans]
+        d_boxes = h2d_async(np.concatenate([c["boxes"].reshape(-1) for c in plans]), dev)      # the one float64 upload
+        rows = [p.det_feats for p, m in zip(problems, m_k) if m]
+        if on_device:
+            feats = [to_dev(r, dev, torch.float32) for r in rows]
+            feats = feats[0] if len(feats) == 1 else torch.cat(feats)
+        else:
+            feats = to_dev(np.concatenate([np.asarray(r, dtype=np.float32) for r in rows]), dev, torch.float32)
+        ctx = self.ctx
+        # the words that go home: [thr [B, 2] as 4 B words, when computed here] | track_det [B, R] | det_track [B, M] | det_slot [B, M] | solver status [2, B]
+        head = 4 * B if data and any(round_k) else 0
+        out = torch.empty(head + B * (R + 2 * M) + 2 * B, dtype=torch.int32, device=dev)
+        base = out.data_ptr() + 4 * head
+        p_track_det, p_det_track, p_det_slot, p_status = base, base + 4 * B * R, base + 4 * B * (R + M), base + 4 * B * (R + 2 * M)
+        out[head + B * (R + 2 * M):].zero_()
+        d_thr = d_fixed
+        slab = None
+        scratch = torch.empty(2 * B * (R + M), dtype=torch.int32, device=dev)
+        sp = scratch.data_ptr()
+        if any(round_k):
+            if head:
+                d_thr = out[:head].view(torch.float64)
+                d_thr.copy_(d_fixed)
+            slab = torch.empty(B, R, M, dtype=torch.float64, device=dev)
+            E = self.E
+
+            def distance(rows, reduce, lo, hi):                    # the tracks lo .. hi - 1 of the matched rows: a whole group, or both
+                groups = (1 if lo == 0 else 0) | (2 if hi == A + I else 0)
+                if rows is None:
+                    args = (g.gallery.data_ptr(), g.count.data_ptr(), self.capacity, 0, self.budget)
+                else:                                              # row i of `rows` is list row lo + i: the table indexed as the slot list starts lo rows before it
+                    args = (rows.data_ptr() - 4 * E * lo, None, n_total, 1, 1)
+                _mgframe_lib.check(mlib.busca_mgframe_distance(*args, feats.data_ptr(), E, _GHOST_REDUCE[reduce.lower() if isinstance(reduce, str) else reduce],
+                                                               groups, *tail, slab.data_ptr(), *where))
+            state = dict(mv_avg=g.mv_avg, mv_seen=g.mv_seen)
+            _ghost_appearance(ctx, state, g.gallery, d_listed[:A + I], g.count, g.newest, A + I, A, feats, first["cfg"], distance=distance)
+            p_tl, p_dl = (d_tl.data_ptr(), d_dl.data_ptr()) if with_labels else (None, None)
+            if data:
+                if with_labels:                                    # solve_hungarian sees the class-masked matrix
+                    _mgframe_lib.check(mlib.busca_mgframe_cost(slab.data_ptr(), None, None, 0.0, p_tl, p_dl, None, *tail, *where))
+                    p_tl = p_dl = None
+                k_act, k_inact = (0.0, 2.0) if first["every"] else (0.5, 1.0)
+                _mgframe_lib.check(mlib.busca_mgframe_thresholds(slab.data_ptr(), k_act, k_inact, 3 if first["data_act"] and first["data_inact"] else 1,
+                                                                 *tail, d_thr.data_ptr(), *where))
+            if p_tl is not None or blend or first["nan_first"]:
+                _mgframe_lib.check(mlib.busca_mgframe_cost(slab.data_ptr(), _lib.ptr(pos) if blend else None, d_boxes.data_ptr(), first["alpha"], p_tl, p_dl,
+                                                           d_thr.data_ptr() if first["nan_first"] else None, *tail, *where))
+
+        def solve(k, row, dims):                                   # the rows from slab row `row` on of every problem: [dims[k, 0], m_k] problems
+            r2c, c2r = sp + 4 * k * B * (R + M), sp + 4 * (k * B * (R + M) + B * R)
+            if slab is not None:
+                ctx.check(ctx.lib.busca_linear_assignment(ctx.h, slab.data_ptr() + 8 * row * M, B, R, M, dims.data_ptr(), float(GHOST_LIMIT), r2c, c2r,
+                                                          None, None, p_status + 4 * k * B, where[1]))
+            return r2c, c2r
+
+        def keep(stage, r2c, c2r, merge, mask):
+            _mgframe_lib.check(mlib.busca_mgframe_keep(_lib.ptr(slab), r2c, c2r, d_thr.data_ptr(), p_track_det, p_det_track, stage, merge, mask, *tail,
+                                                       *where))
+        if not sep:
+            keep(0, *solve(0, 0, d_dims1), 0, 0)
+        else:
+            keep(1, *solve(0, 0, d_dims1), 0, 1 if R > NA else 0)
+            if R > NA:
+                keep(2, *solve(1, NA, d_dims2), 1, 0)
+        if apply:
+            _mgframe_lib.check(mlib.busca_mgframe_apply(
+                *rings, self.history, g._gallery.data_ptr(), g._count.data_ptr(), g._newest.data_ptr(), g._mv_seen.data_ptr(), self.budget, self.E,
+                p_track_det if R else None, p_det_track, feats.data_ptr(), d_boxes.data_ptr(), d_may.data_ptr(), d_free.data_ptr() if f_total else None,
+                *tail, p_det_slot, *where))
+        host = out.cpu().numpy()                                   # the one device->host copy
+        body = host[head:]
+        track_det, det_track, det_slot = body[:B * R].reshape(B, R), body[B * R:B * (R + M)].reshape(B, M), body[B * (R + M):B * (R + 2 * M)].reshape(B, M)
+        status = body[B * (R + 2 * M):].reshape(2, B)
+        for k in range(B):                                         # in the order frame() raises, problem by problem
+            if status[:, k].any():
+                raise _lib.BuscaError("%s: problem %d: the solver ran out of its loop bounds (status %s) - is a cost -inf?"
+                                      % (what, k, status[:, k].tolist()))
+        frames = []
+        for k, c in enumerate(plans):
+            na, ni, m = na_k[k], ni_k[k], m_k[k]
+            n = na + ni
+            if m == 0:
+                frames.append(_no_frame(c["na"], c["n"] - c["na"]))
+                continue
+            thr = tuple(float(x) for x in (host[4 * k:4 * k + 4].view(np.float64) if head and round_k[k] else c["fixed"]))
+            # the words of problem k are its corner of the blocks: the kernels write nothing else, and nothing else is read
+            td = np.concatenate([track_det[k, :na], track_det[k, NA:NA + ni]]) if sep else track_det[k, :n]
+            dt, ds = det_track[k, :m], det_slot[k, :m]
+            matches = [(int(i), int(td[i])) for i in range(n) if td[i] >= 0]
+            new, overflow = [], []
+            if apply:
+                new = [(j, int(ds[j])) for j in range(m) if dt[j] < 0 and ds[j] >= 0]
+                overflow = [j for j in range(m) if ds[j] == -2]
+            dist = None
+            if round_k[k]:
+                dist = [slab[k, :na, :m].T, slab[k, NA:NA + ni, :m].T if na > 0 else None] if sep else slab[k, :n, :m].T
+            frames.append(GhostFrame(matches, new, overflow, [i for i in range(na) if td[i] < 0], [i for i in range(na, n) if td[i] < 0], thr, dist))
+        return frames
+
+
+GhostFrameProblem = namedtuple("GhostFrameProblem", "active inactive det_feats det_boxes frame det_conf idle free_slots labels warp all_warped",
+                               defaults=(None, (), (), None, None, False))
+GhostFrameProblem.__doc__ = """One sequence's frame of GhostStore.frame_batch: the arguments of GhostStore.frame with their meaning there, and
+  all_warped   every stored row of this sequence has been warped since its last detection was added: what GhostStore.all_warped_after returned
+               for its previous step (False at the start) - GhostMotion.all_warped, per sequence"""

@@ -34,7 +34,7 @@ from .geometry import box_extents  # noqa: F401
 from .ghost import GHOST_LIMIT, ghost_check_config, ghost_cost, ghost_distance, ghost_proxies, ghost_round, ghost_thresholds  # noqa: F401
 from .ghost_gallery import GhostGallery  # noqa: F401
 from .ghost_motion import GhostMotion, ghost_motion_check_config  # noqa: F401
-from .ghost_store import GhostFrame, GhostStore  # noqa: F401
+from .ghost_store import GhostFrame, GhostFrameProblem, GhostStore  # noqa: F401
 from .kalman import (CHI2INV95, TRACKED, fuse_motion, gate_cost_matrix, gating_distance, multi_initiate, multi_predict, multi_update,  # noqa: F401
                      predicted_cost, tlwh_to_xyah)
 from .kalman_store import ByteFrame, FrameProblem, KalmanStore, RoundProblem  # noqa: F401
