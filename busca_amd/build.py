@@ -1,7 +1,8 @@
-"""Build libbusca_hip.so, libbusca_track.so, libbusca_store.so, libbusca_rounds.so, libbusca_sort.so, libbusca_frame.so, libbusca_sframe.so, libbusca_mframe.so, libbusca_msframe.so, libbusca_gframe.so and libbusca_mgframe.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build the libraries of LIBS below - libbusca_hip.so and the context-free libbusca_<stem>.so - in-tree with hipcc for gfx950 (cross-compiles without
+a GPU).
 
-The library is several translation units (csrc/busca_internal.hpp lists them) compiled IN PARALLEL into busca_amd/build/*.o and linked: a full build is
-as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
+A library is one or several translation units (csrc/busca_internal.hpp lists those of libbusca_hip.so) compiled IN PARALLEL into busca_amd/build/*.o
+and linked: a full build is as long as its slowest unit, and an edit recompiles only the units that include the edited file."""
 import os
 import re
 import subprocess
@@ -11,70 +12,50 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
-OUT = os.path.join(HERE, "libbusca_hip.so")
-STAMP = OUT + ".flags"
-# (unit, compiled with -amdgpu-mfma-vgpr-form where that compiles).  busca_dt_aux: the instantiations that crash that pass (see the file).
-UNITS = [("busca_hip", True), ("busca_dt_f32", True), ("busca_dt_f16", True), ("busca_dt_x3", True), ("busca_dt_aux", False),
-         ("busca_dtl_f32", True), ("busca_dtl_f16", True), ("busca_dtl_x3", True), ("busca_reid", True), ("busca_assign", False), ("busca_appear", False), ("busca_ghost", False), ("busca_ghost_motion", False)]
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-HEADERS = ["busca_hip.h", "busca_assign.h", "busca_assign_stages.h", "busca_appearance.h", "busca_ghost.h", "busca_ghost_motion.h", "busca_reid_bn.h", "busca_ecc.h"]
-# libbusca_track.so (include/busca_track.h): the context-free library of device-resident tracker state.  Its own units, objects, stamp and staleness
-# check; the same flags, no MFMA in it.  It shares kernel includes with busca_hip (track_kernel, pairwise_kernel), so an edit there rebuilds both.
-TRACK_OUT = os.path.join(HERE, "libbusca_track.so")
-TRACK_UNITS = [("busca_track", False)]
-TRACK_HEADERS = ["busca_track.h", "busca_hip.h"]
-# libbusca_store.so (include/busca_store.h): the context-free library of device-resident appearance state.  Handled exactly as the track library; it
-# shares no kernel text with the other two.
-STORE_OUT = os.path.join(HERE, "libbusca_store.so")
-STORE_UNITS = [("busca_store", False)]
-STORE_HEADERS = ["busca_store.h"]
-# libbusca_rounds.so (include/busca_rounds.h): the context-free library of association rounds batched across sequences.  Handled as the two above; it
-# compiles the kernel includes of the track library (and kalman_store_kernel with them), so an edit there rebuilds both.
-ROUNDS_OUT = os.path.join(HERE, "libbusca_rounds.so")
-ROUNDS_UNITS = [("busca_rounds", False)]
-ROUNDS_HEADERS = ["busca_rounds.h", "busca_hip.h"]
-# libbusca_sort.so (include/busca_sort.h): the context-free library of StrongSORT's device-resident track state.  Handled as the three above; it
-# compiles the kernel includes of the track library under its own sort_kernel, so an edit there rebuilds it too.
-SORT_OUT = os.path.join(HERE, "libbusca_sort.so")
-SORT_UNITS = [("busca_sort", False)]
-SORT_HEADERS = ["busca_sort.h", "busca_hip.h"]
-# libbusca_frame.so (include/busca_frame.h): the context-free library of a ByteTrack frame on resident state - the cost slab of the three rounds and
-# the match vectors applied to the Kalman state.  Handled as the four above; it compiles the kernel includes of the track library under its own
-# frame_kernel, so an edit there rebuilds it too.
-FRAME_OUT = os.path.join(HERE, "libbusca_frame.so")
-FRAME_UNITS = [("busca_frame", False)]
-FRAME_HEADERS = ["busca_frame.h", "busca_hip.h"]
-# libbusca_sframe.so (include/busca_sframe.h): the context-free library of a StrongSORT frame on resident state - the camera update with predict, the
-# cost slab of Tracker._match and the match vectors applied to the Kalman state and the feature rows.  Handled as the five above; it compiles the kernel
-# includes of the sort and store libraries under its own sframe_kernel, so an edit there rebuilds it too.
-SFRAME_OUT = os.path.join(HERE, "libbusca_sframe.so")
-SFRAME_UNITS = [("busca_sframe", False)]
-SFRAME_HEADERS = ["busca_sframe.h", "busca_hip.h"]
-# libbusca_mframe.so (include/busca_mframe.h): the context-free library of the ByteTrack frames of many sequences on one store - the ragged batched
-# forms of the two calls of libbusca_frame.so.  Handled as the six above; it compiles frame_kernel and the kernel includes below it under its own
-# mframe_kernel, so an edit there rebuilds it too.
-MFRAME_OUT = os.path.join(HERE, "libbusca_mframe.so")
-MFRAME_UNITS = [("busca_mframe", False)]
-MFRAME_HEADERS = ["busca_mframe.h", "busca_frame.h", "busca_hip.h"]
-# libbusca_msframe.so (include/busca_msframe.h): the context-free library of the StrongSORT frames of many sequences on one store - the ragged batched
-# forms of the three calls of libbusca_sframe.so, with the appearance tile of busca_appearance_cost inside the cost kernel.  Handled as the seven
-# above; it compiles sframe_kernel, appear_kernel and the kernel includes below them under its own msframe_kernel, so an edit there rebuilds it too.
-MSFRAME_OUT = os.path.join(HERE, "libbusca_msframe.so")
-MSFRAME_UNITS = [("busca_msframe", False)]
-MSFRAME_HEADERS = ["busca_msframe.h", "busca_sframe.h", "busca_appearance.h", "busca_hip.h"]
-# libbusca_gframe.so (include/busca_gframe.h): the context-free library of a GHOST frame on resident state - the warp with the motion step, the final
-# cost matrix, the threshold filter on the solver's matches and the kept matches applied to the position and feature rings.  Handled as the eight
-# above; it compiles the kernel includes of the GHOST units of libbusca_hip.so and of the store library under its own gframe_kernel, so an edit
-# there rebuilds it too.
-GFRAME_OUT = os.path.join(HERE, "libbusca_gframe.so")
-GFRAME_UNITS = [("busca_gframe", False)]
-GFRAME_HEADERS = ["busca_gframe.h", "busca_ghost.h", "busca_appearance.h", "busca_hip.h"]
-# libbusca_mgframe.so (include/busca_mgframe.h): the context-free library of the GHOST frames of many sequences on one store - the ragged batched
-# forms of the four calls of libbusca_gframe.so and of busca_ghost_distance / busca_ghost_thresholds.  Handled as the nine above; it compiles
-# gframe_kernel, ghost_kernel and the kernel includes below them under its own mgframe_kernel, so an edit there rebuilds it too.
-MGFRAME_OUT = os.path.join(HERE, "libbusca_mgframe.so")
-MGFRAME_UNITS = [("busca_mgframe", False)]
-MGFRAME_HEADERS = ["busca_mgframe.h", "busca_gframe.h", "busca_ghost.h", "busca_appearance.h", "busca_hip.h"]
+# (stem, units, headers) of libbusca_<stem>.so, in build order.  A unit is (name, compiled with -amdgpu-mfma-vgpr-form where that compiles); the first
+# header is the library's own under include/.  Each library has its own objects, stamp and staleness check (_build_lib) and the same flags.  All but
+# the last are context-free: one unit without MFMA, the host plumbing of csrc/capi_prelude.hpp, bound by busca_amd/_<stem>_lib.py.  They compile
+# kernel includes whole, so an edit to one rebuilds every library named with it here.
+LIBS = [
+    # device-resident tracker state; shares track_kernel and pairwise_kernel with hip
+    ("track", [("busca_track", False)], ["busca_track.h", "busca_hip.h"]),
+    # device-resident appearance state; store_kernel alone, shared with no library above
+    ("store", [("busca_store", False)], ["busca_store.h"]),
+    # association rounds batched across sequences; track's kernel includes (with kalman_store_kernel) under rounds_kernel
+    ("rounds", [("busca_rounds", False)], ["busca_rounds.h", "busca_hip.h"]),
+    # StrongSORT's device-resident track state; track's kernel includes under sort_kernel
+    ("sort", [("busca_sort", False)], ["busca_sort.h", "busca_hip.h"]),
+    # a ByteTrack frame on resident state; track's kernel includes under frame_kernel
+    ("frame", [("busca_frame", False)], ["busca_frame.h", "busca_hip.h"]),
+    # a StrongSORT frame on resident state; sort's and store's kernel includes under sframe_kernel
+    ("sframe", [("busca_sframe", False)], ["busca_sframe.h", "busca_hip.h"]),
+    # ByteTrack frames of many sequences; frame's kernel includes under mframe_kernel
+    ("mframe", [("busca_mframe", False)], ["busca_mframe.h", "busca_frame.h", "busca_hip.h"]),
+    # StrongSORT frames of many sequences; sframe's kernel includes and hip's appear_kernel under msframe_kernel
+    ("msframe", [("busca_msframe", False)], ["busca_msframe.h", "busca_sframe.h", "busca_appearance.h", "busca_hip.h"]),
+    # a GHOST frame on resident state; the kernel includes of hip's GHOST units and store's under gframe_kernel
+    ("gframe", [("busca_gframe", False)], ["busca_gframe.h", "busca_ghost.h", "busca_appearance.h", "busca_hip.h"]),
+    # GHOST frames of many sequences; gframe's kernel includes under mgframe_kernel
+    ("mgframe", [("busca_mgframe", False)], ["busca_mgframe.h", "busca_gframe.h", "busca_ghost.h", "busca_appearance.h", "busca_hip.h"]),
+    # the context-bound library (busca_ctx).  busca_dt_aux: the instantiations that crash the vgpr-form pass (see the file)
+    ("hip", [("busca_hip", True), ("busca_dt_f32", True), ("busca_dt_f16", True), ("busca_dt_x3", True), ("busca_dt_aux", False),
+             ("busca_dtl_f32", True), ("busca_dtl_f16", True), ("busca_dtl_x3", True), ("busca_reid", True), ("busca_assign", False),
+             ("busca_appear", False), ("busca_ghost", False), ("busca_ghost_motion", False)],
+     ["busca_hip.h", "busca_assign.h", "busca_assign_stages.h", "busca_appearance.h", "busca_ghost.h", "busca_ghost_motion.h", "busca_reid_bn.h",
+      "busca_ecc.h"]),
+]
+
+
+def lib_path(stem):
+    return os.path.join(HERE, "libbusca_%s.so" % stem)
+
+
+# TRACK_OUT ... MGFRAME_OUT: the paths the bindings load; OUT, UNITS, HEADERS, STAMP: those of libbusca_hip.so
+for _stem, _units, _headers in LIBS[:-1]:
+    globals()[_stem.upper() + "_OUT"] = lib_path(_stem)
+OUT, (_, UNITS, HEADERS) = lib_path("hip"), LIBS[-1]
+STAMP = OUT + ".flags"
 
 
 def _requested_flags():
@@ -179,18 +160,10 @@ def _build_lib(out, units, headers, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """(Re)build what is stale of the eleven libraries, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
-    _build_lib(TRACK_OUT, TRACK_UNITS, TRACK_HEADERS, force, verbose)
-    _build_lib(STORE_OUT, STORE_UNITS, STORE_HEADERS, force, verbose)
-    _build_lib(ROUNDS_OUT, ROUNDS_UNITS, ROUNDS_HEADERS, force, verbose)
-    _build_lib(SORT_OUT, SORT_UNITS, SORT_HEADERS, force, verbose)
-    _build_lib(FRAME_OUT, FRAME_UNITS, FRAME_HEADERS, force, verbose)
-    _build_lib(SFRAME_OUT, SFRAME_UNITS, SFRAME_HEADERS, force, verbose)
-    _build_lib(MFRAME_OUT, MFRAME_UNITS, MFRAME_HEADERS, force, verbose)
-    _build_lib(MSFRAME_OUT, MSFRAME_UNITS, MSFRAME_HEADERS, force, verbose)
-    _build_lib(GFRAME_OUT, GFRAME_UNITS, GFRAME_HEADERS, force, verbose)
-    _build_lib(MGFRAME_OUT, MGFRAME_UNITS, MGFRAME_HEADERS, force, verbose)
-    return _build_lib(OUT, UNITS, HEADERS, force, verbose)
+    """(Re)build what is stale of the libraries of LIBS, each by its own unit list, objects and stamp (_build_lib) -> the path of libbusca_hip.so."""
+    for stem, units, headers in LIBS:
+        _build_lib(lib_path(stem), units, headers, force, verbose)
+    return OUT
 
 
 if __name__ == "__main__":

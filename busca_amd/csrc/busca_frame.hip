@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -25,40 +24,8 @@
 #include "kalman_store_kernel.hip.inc"
 #include "frame_kernel.hip.inc"
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define FRAME_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                     \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_FRAME_EHIP, "%s: %s", who, hipGetErrorString(scope.err));      \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_FRAME_EHIP, "%s: %s", who, hipGetErrorString(e_));                    \
-    } while (0)
+#define CAPI_EHIP BUSCA_FRAME_EHIP
+#include "capi_prelude.hpp"
 
 extern "C" int busca_frame_version(void) { return 1000; }
 
@@ -79,8 +46,8 @@ extern "C" int busca_frame_cost(const double* mean, const double* cov, int32_t S
     const long long row_tiles = ((long long)n + PW_TA - 1) / PW_TA, col_tiles = ((long long)m + PW_TB - 1) / PW_TB;
     if (row_tiles > 65535) return refuse(BUSCA_FRAME_EINVAL, "%s: %d tracks need more workgroups than a grid holds (%d at most)", who, n, 65535 * PW_TA);
     const KStore k{(double*)mean, (double*)cov, (const int*)slot, S, n};       // the covariances are not read: a box is a function of the mean
-    FRAME_LAUNCH(who, device, frame_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, k, det_tlbr, det_score, det_class, m,
-                 out, (int*)status);
+    CAPI_LAUNCH(who, device, frame_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, k, det_tlbr, det_score, det_class, m,
+                out, (int*)status);
     return 0;
 }
 
@@ -110,6 +77,6 @@ extern "C" int busca_frame_apply(double* mean, double* cov, int32_t S, const int
     f.det_xyah = det_xyah, f.det_score = det_score, f.det_class = det_class;
     f.free_slot = (const int*)free_slot, f.new_slot = (int*)new_slot, f.status = (int*)status;
     f.det_thresh = det_thresh, f.m = m, f.n_free = n_free;
-    FRAME_LAUNCH(who, device, frame_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, k, f);
+    CAPI_LAUNCH(who, device, frame_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, k, f);
     return 0;
 }

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -29,40 +28,8 @@
 #include "store_kernel.hip.inc"
 #include "gframe_kernel.hip.inc"
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define GFRAME_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                    \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_GFRAME_EHIP, "%s: %s", who, hipGetErrorString(scope.err));     \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_GFRAME_EHIP, "%s: %s", who, hipGetErrorString(e_));                   \
-    } while (0)
+#define CAPI_EHIP BUSCA_GFRAME_EHIP
+#include "capi_prelude.hpp"
 
 extern "C" int busca_gframe_version(void) { return 1000; }
 
@@ -90,7 +57,7 @@ extern "C" int busca_gframe_advance(double* hist, const int32_t* frames, const i
     a.r = GhostMotionRings{hist, (int*)frames, (int*)count, (int*)newest, pos, vel, S, H};
     a.slot = (const int*)slot, a.warp = warp, a.out = pos_out;
     a.n = warp ? n : n_step, a.n_step = n_step, a.num_active = num_active, a.last_n = last_n_frames, a.diff32 = diff32 != 0;
-    GFRAME_LAUNCH(who, device, gframe_advance_kernel, dim3((unsigned)a.n), dim3(64), stream, a);
+    CAPI_LAUNCH(who, device, gframe_advance_kernel, dim3((unsigned)a.n), dim3(64), stream, a);
     return 0;
 }
 
@@ -116,7 +83,7 @@ extern "C" int busca_gframe_cost(const double* app, const double* pos, const dou
     const int na = num_active < 0 ? 0 : num_active > n ? n : num_active;      // for a row i < n, i < num_active is i < na
     a.rows = GFrameRows{na, n - na, 0, na, na};                   // row i of the matrix is row i of pos and track_label
     a.m = m, a.ld = m;
-    GFRAME_LAUNCH(who, device, gframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, a);
+    CAPI_LAUNCH(who, device, gframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, a);
     return 0;
 }
 
@@ -142,7 +109,7 @@ extern "C" int busca_gframe_keep(double* cost, int32_t n, int32_t m, int32_t lo,
     a.track_det = (int*)track_det, a.det_track = (int*)det_track;
     a.m = m, a.ld = m, a.lo = lo, a.hi = hi, a.num_active = num_active, a.merge = merge != 0, a.mask_from = mask_from, a.mask_to = n;
     const int threads = hi - lo > m ? hi - lo : m;
-    GFRAME_LAUNCH(who, device, gframe_keep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), stream, a);
+    CAPI_LAUNCH(who, device, gframe_keep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), stream, a);
     return 0;
 }
 
@@ -179,6 +146,6 @@ extern "C" int busca_gframe_apply(double* hist, int32_t* frames, int32_t* m_coun
     f.det_feat = det_feat, f.det_boxes = det_boxes, f.may_start = may_start, f.free_slot = (const int*)free_slot, f.det_slot = (int*)det_slot;
     f.rows = GFrameRows{n, 0, 0, 0, n};                           // row i of the matrix is slot[i]
     f.m = m, f.budget = budget, f.E = E, f.frame = frame, f.n_free = n_free;
-    GFRAME_LAUNCH(who, device, gframe_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, f, (int)n);
+    CAPI_LAUNCH(who, device, gframe_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, f, (int)n);
     return 0;
 }

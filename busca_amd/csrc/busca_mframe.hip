@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -29,40 +28,8 @@ static_assert(BUSCA_MFRAME_MAX_DETS == BUSCA_FRAME_MAX_DETS, "one limit for a pr
 #include "frame_kernel.hip.inc"
 #include "mframe_kernel.hip.inc"
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define MFRAME_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                    \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_MFRAME_EHIP, "%s: %s", who, hipGetErrorString(scope.err));     \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_MFRAME_EHIP, "%s: %s", who, hipGetErrorString(e_));                   \
-    } while (0)
+#define CAPI_EHIP BUSCA_MFRAME_EHIP
+#include "capi_prelude.hpp"
 
 // the sizes both calls take, judged alike
 static int sizes_refused(const char* who, int32_t S, int32_t n_total, int32_t m_total, int32_t f_total, int32_t batch, int32_t N, int32_t M,
@@ -97,8 +64,8 @@ extern "C" int busca_mframe_cost(const double* mean, const double* cov, int32_t 
     MFrame b;
     b.slot = (const int*)slot, b.free_slot = nullptr, b.problems = (const int*)problems;
     b.S = S, b.n_total = n_total, b.m_total = m_total, b.f_total = f_total, b.N = N, b.M = M;
-    MFRAME_LAUNCH(who, device, mframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles, (unsigned)batch), dim3(256), stream, b, mean, det_tlbr,
-                  det_score, det_class, out, (int*)status);
+    CAPI_LAUNCH(who, device, mframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles, (unsigned)batch), dim3(256), stream, b, mean, det_tlbr,
+                det_score, det_class, out, (int*)status);
     return 0;
 }
 
@@ -132,6 +99,6 @@ extern "C" int busca_mframe_apply(double* mean, double* cov, int32_t S, const in
     f.det_xyah = det_xyah, f.det_score = det_score, f.det_class = det_class;
     f.free_slot = nullptr, f.new_slot = (int*)new_slot, f.status = (int*)status;
     f.det_thresh = det_thresh, f.m = 0, f.n_free = 0;
-    MFRAME_LAUNCH(who, device, mframe_apply_kernel, dim3((unsigned)((long long)N + M), (unsigned)batch), dim3(64), stream, b, mean, cov, f);
+    CAPI_LAUNCH(who, device, mframe_apply_kernel, dim3((unsigned)((long long)N + M), (unsigned)batch), dim3(64), stream, b, mean, cov, f);
     return 0;
 }

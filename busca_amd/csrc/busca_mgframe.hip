@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -37,42 +36,8 @@ static_assert(BUSCA_MGFRAME_MAX_DETS == BUSCA_GFRAME_MAX_DETS, "one limit for a 
 static_assert(BUSCA_MGFRAME_E_MIN == BUSCA_APPEAR_E_MIN && BUSCA_MGFRAME_E_MAX == BUSCA_APPEAR_E_MAX, "the feature widths busca_ghost_distance takes");
 static_assert(BUSCA_MGFRAME_MEDIAN_BUDGET_MAX == BUSCA_GHOST_MEDIAN_BUDGET_MAX, "one budget limit for MEDIAN");
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define MGFRAME_LAUNCH(who, device, kernel, grid, block, lds, stream, ...)                                              \
-    do {                                                                                                                \
-        hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)(stream), __VA_ARGS__);                               \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_MGFRAME_EHIP, "%s: %s", who, hipGetErrorString(e_));                  \
-    } while (0)
-
-#define MGFRAME_SCOPE(who, device)                                                                                      \
-    DeviceScope scope(device);                                                                                          \
-    if (scope.err != hipSuccess) return refuse(BUSCA_MGFRAME_EHIP, "%s: %s", who, hipGetErrorString(scope.err))
+#define CAPI_EHIP BUSCA_MGFRAME_EHIP
+#include "capi_prelude.hpp"
 
 // what every call takes, judged alike
 struct Sizes {
@@ -126,8 +91,8 @@ extern "C" int busca_mgframe_advance(double* hist, const int32_t* frames, const 
         return refuse(BUSCA_MGFRAME_EINVAL, "%s: misaligned pointer (8 bytes for float64, 4 for int32 and float32)", who);
     const MGFrame b = table_of(z, slot, nullptr, problems, warps);
     const GhostMotionRings r{hist, (int*)frames, (int*)count, (int*)newest, pos, vel, S, H};
-    MGFRAME_SCOPE(who, device);
-    MGFRAME_LAUNCH(who, device, mgframe_advance_kernel, dim3((unsigned)L, (unsigned)batch), dim3(64), 0, stream, b, r, (int)last_n_frames, pos_out);
+    CAPI_SCOPE(who, device);
+    CAPI_LAUNCH_IN_SCOPE(who, mgframe_advance_kernel, dim3((unsigned)L, (unsigned)batch), dim3(64), 0, stream, b, r, (int)last_n_frames, pos_out);
     return 0;
 }
 
@@ -160,14 +125,14 @@ extern "C" int busca_mgframe_distance(const float* gallery, const int32_t* count
     const MGFrame b = table_of(z, slot, nullptr, problems, nullptr);
     const MGFrameDist d{gallery, (const int*)count, dets, out, rows, by_list != 0, budget, E, reduce, groups};
     const dim3 grid((unsigned)(((long long)M + APPEAR_TILE_M - 1) / APPEAR_TILE_M), (unsigned)R, (unsigned)batch), block(64 * APPEAR_WAVES);
-    MGFRAME_SCOPE(who, device);
+    CAPI_SCOPE(who, device);
     if (reduce == BUSCA_GHOST_MEDIAN) {
         const size_t top = ((size_t)BUSCA_MGFRAME_MEDIAN_BUDGET_MAX + 2) * APPEAR_TILE_M * sizeof(double);
         const hipError_t e = hipFuncSetAttribute((const void*)mgframe_distance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)top);
         if (e != hipSuccess) return refuse(BUSCA_MGFRAME_EHIP, "%s: %s", who, hipGetErrorString(e));
-        MGFRAME_LAUNCH(who, device, (mgframe_distance_kernel<true>), grid, block, ((size_t)budget + 2) * APPEAR_TILE_M * sizeof(double), stream, b, d);
+        CAPI_LAUNCH_IN_SCOPE(who, (mgframe_distance_kernel<true>), grid, block, ((size_t)budget + 2) * APPEAR_TILE_M * sizeof(double), stream, b, d);
     } else {
-        MGFRAME_LAUNCH(who, device, (mgframe_distance_kernel<false>), grid, block, 0, stream, b, d);
+        CAPI_LAUNCH_IN_SCOPE(who, (mgframe_distance_kernel<false>), grid, block, 0, stream, b, d);
     }
     return 0;
 }
@@ -186,8 +151,8 @@ extern "C" int busca_mgframe_thresholds(const double* cost, double k_act, double
         return refuse(BUSCA_MGFRAME_EINVAL, "%s: misaligned pointer (8 bytes for float64, 4 for int32)", who);
     (void)slot;
     const MGFrame b = table_of(z, nullptr, nullptr, problems, nullptr);
-    MGFRAME_SCOPE(who, device);
-    MGFRAME_LAUNCH(who, device, mgframe_thresholds_kernel, dim3((unsigned)batch), dim3(GHOST_THR_THREADS), 0, stream, b, cost, k_act, k_inact, (int)which, thr);
+    CAPI_SCOPE(who, device);
+    CAPI_LAUNCH_IN_SCOPE(who, mgframe_thresholds_kernel, dim3((unsigned)batch), dim3(GHOST_THR_THREADS), 0, stream, b, cost, k_act, k_inact, (int)which, thr);
     return 0;
 }
 
@@ -214,8 +179,8 @@ extern "C" int busca_mgframe_cost(double* cost, const double* pos, const double*
     a.w_app = 1.0 - alpha, a.w_motion = alpha;                    // as busca_ghost_combine forms them
     a.rows = GFrameRows{0, 0, 0, 0, 0}, a.m = 0, a.ld = 0;        // the problem's: set by the kernel
     const dim3 grid((unsigned)(((long long)M + PW_TB - 1) / PW_TB), (unsigned)(((long long)R + PW_TA - 1) / PW_TA), (unsigned)batch);
-    MGFRAME_SCOPE(who, device);
-    MGFRAME_LAUNCH(who, device, mgframe_cost_kernel, grid, dim3(256), 0, stream, b, a);
+    CAPI_SCOPE(who, device);
+    CAPI_LAUNCH_IN_SCOPE(who, mgframe_cost_kernel, grid, dim3(256), 0, stream, b, a);
     return 0;
 }
 
@@ -243,9 +208,9 @@ extern "C" int busca_mgframe_keep(double* cost, const int32_t* row_to_col, const
     a.track_det = (int*)track_det, a.det_track = (int*)det_track;
     a.m = 0, a.ld = 0, a.lo = 0, a.hi = 0, a.num_active = 0, a.merge = merge != 0, a.mask_from = -1, a.mask_to = 0;      // the rest is the problem's
     const int threads = R > M ? R : M;
-    MGFRAME_SCOPE(who, device);
-    MGFRAME_LAUNCH(who, device, mgframe_keep_kernel, dim3((unsigned)((threads + 255) / 256), (unsigned)batch), dim3(256), 0, stream, b, a, (int)stage,
-                   (int)(mask != 0));
+    CAPI_SCOPE(who, device);
+    CAPI_LAUNCH_IN_SCOPE(who, mgframe_keep_kernel, dim3((unsigned)((threads + 255) / 256), (unsigned)batch), dim3(256), 0, stream, b, a, (int)stage,
+                         (int)(mask != 0));
     return 0;
 }
 
@@ -285,7 +250,7 @@ extern "C" int busca_mgframe_apply(double* hist, int32_t* frames, int32_t* m_cou
     f.slot = (const int*)slot, f.track_det = (const int*)track_det, f.det_track = (const int*)det_track;
     f.det_feat = det_feat, f.det_boxes = det_boxes, f.may_start = may_start, f.free_slot = nullptr, f.det_slot = (int*)det_slot;
     f.rows = GFrameRows{0, 0, 0, 0, 0}, f.m = 0, f.budget = budget, f.E = E, f.frame = 0, f.n_free = 0;      // rows, m, frame and n_free are the problem's
-    MGFRAME_SCOPE(who, device);
-    MGFRAME_LAUNCH(who, device, mgframe_apply_kernel, dim3((unsigned)(b.R + M), (unsigned)batch), dim3(64), 0, stream, b, f);
+    CAPI_SCOPE(who, device);
+    CAPI_LAUNCH_IN_SCOPE(who, mgframe_apply_kernel, dim3((unsigned)(b.R + M), (unsigned)batch), dim3(64), 0, stream, b, f);
     return 0;
 }

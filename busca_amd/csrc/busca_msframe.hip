@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -37,40 +36,8 @@ static_assert(BUSCA_MSFRAME_MAX_DETS == BUSCA_SFRAME_MAX_DETS, "one limit for a 
 static_assert(BUSCA_MSFRAME_E_MIN == BUSCA_APPEAR_E_MIN && BUSCA_MSFRAME_E_MAX == BUSCA_APPEAR_E_MAX, "the feature widths busca_appearance_cost takes");
 static_assert(STORE_THREADS == 256, "sframe_wave_norm restates the norm of a 256-thread store_block_norm");
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define MSFRAME_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                   \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_MSFRAME_EHIP, "%s: %s", who, hipGetErrorString(scope.err));    \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_MSFRAME_EHIP, "%s: %s", who, hipGetErrorString(e_));                  \
-    } while (0)
+#define CAPI_EHIP BUSCA_MSFRAME_EHIP
+#include "capi_prelude.hpp"
 
 // the sizes all three calls take, judged alike
 static int sizes_refused(const char* who, int32_t S, int32_t n_total, int32_t m_total, int32_t f_total, int32_t n_matrices, int32_t batch, int32_t N,
@@ -109,7 +76,7 @@ extern "C" int busca_msframe_advance(double* mean, double* cov, int32_t S, const
     if (misaligned(mean, 8) || misaligned(cov, 8) || misaligned(matrices, 8) || misaligned(slot, 4) || misaligned(problems, 4))
         return refuse(BUSCA_MSFRAME_EINVAL, "%s: misaligned pointer (8 bytes for float64, 4 for int32)", who);
     const MSFrame b = table_of(slot, nullptr, problems, matrices, S, n_total, m_total, f_total, n_matrices, N, M);
-    MSFRAME_LAUNCH(who, device, msframe_advance_kernel, dim3((unsigned)N, (unsigned)batch), dim3(64), stream, b, mean, cov);
+    CAPI_LAUNCH(who, device, msframe_advance_kernel, dim3((unsigned)N, (unsigned)batch), dim3(64), stream, b, mean, cov);
     return 0;
 }
 
@@ -148,8 +115,8 @@ extern "C" int busca_msframe_cost(const double* mean, const double* cov, int32_t
     a.gated_cost = gated_cost, a.lambda = mc_lambda, a.rest = 1.0 - mc_lambda, a.max_distance = max_distance, a.limit = max_distance + 1e-5;
     a.max_iou = max_iou_distance, a.iou_limit = max_iou_distance + 1e-5;
     a.m = 0, a.ld_cost = 0, a.flags = flags, a.depth = depth;
-    MSFRAME_LAUNCH(who, device, msframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles, (unsigned)batch), dim3(256), stream, b, mean, cov, a,
-                   feat, det_feat, (int)E);
+    CAPI_LAUNCH(who, device, msframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles, (unsigned)batch), dim3(256), stream, b, mean, cov, a,
+                feat, det_feat, (int)E);
     return 0;
 }
 
@@ -183,6 +150,6 @@ extern "C" int busca_msframe_apply(double* mean, double* cov, int32_t S, const i
     f.free_slot = nullptr, f.new_slot = (int*)new_slot, f.status = (int*)status;
     f.wa = (float)alpha, f.wb = (float)(1.0 - alpha);      // as busca_store_ema_fit forms them: the subtraction in float64, each rounded once
     f.m = 0, f.E = E, f.n_free = 0;
-    MSFRAME_LAUNCH(who, device, msframe_apply_kernel, dim3((unsigned)((long long)N + M), (unsigned)batch), dim3(64), stream, b, mean, cov, f);
+    CAPI_LAUNCH(who, device, msframe_apply_kernel, dim3((unsigned)((long long)N + M), (unsigned)batch), dim3(64), stream, b, mean, cov, f);
     return 0;
 }

@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -27,31 +26,8 @@
 static_assert(KSTORE_FUSE_MOTION == BUSCA_ROUNDS_FUSE_MOTION && KSTORE_ONLY_POSITION == BUSCA_ROUNDS_ONLY_POSITION && KSTORE_GATE_ONLY == BUSCA_ROUNDS_GATE_ONLY,
               "kalman_store_kernel.hip.inc and busca_rounds.h disagree on the flags");
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+#define CAPI_EHIP BUSCA_ROUNDS_EHIP
+#include "capi_prelude.hpp"
 
 extern "C" int busca_rounds_version(void) { return 1000; }
 
@@ -86,10 +62,6 @@ extern "C" int busca_rounds_cost(const double* mean, const double* cov, int32_t 
     r.det_tlbr = det_tlbr, r.det_xyah = motion ? det_xyah : nullptr, r.det_score = det_score;
     r.problems = (const int*)problems, r.out = out, r.status = (int*)status, r.lambda = lambda;
     r.S = S, r.n_total = n_total, r.m_total = m_total, r.N = N, r.M = M, r.flags = flags;
-    DeviceScope scope(device);
-    if (scope.err != hipSuccess) return refuse(BUSCA_ROUNDS_EHIP, "%s: %s", who, hipGetErrorString(scope.err));
-    hipLaunchKernelGGL(rounds_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, r);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return refuse(BUSCA_ROUNDS_EHIP, "%s: %s", who, hipGetErrorString(e));
+    CAPI_LAUNCH(who, device, rounds_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles, (unsigned)batch), dim3(256), stream, r);
     return 0;
 }

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -30,40 +29,8 @@
 static_assert(SORT_MC == BUSCA_SFRAME_MC && SORT_CLAMP == BUSCA_SFRAME_CLAMP, "sort_kernel.hip.inc and busca_sframe.h disagree on the flags");
 static_assert(STORE_THREADS == 256, "sframe_wave_norm restates the norm of a 256-thread store_block_norm");
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define SFRAME_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                    \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_SFRAME_EHIP, "%s: %s", who, hipGetErrorString(scope.err));     \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_SFRAME_EHIP, "%s: %s", who, hipGetErrorString(e_));                   \
-    } while (0)
+#define CAPI_EHIP BUSCA_SFRAME_EHIP
+#include "capi_prelude.hpp"
 
 extern "C" int busca_sframe_version(void) { return 1001; }
 
@@ -79,7 +46,7 @@ extern "C" int busca_sframe_advance(double* mean, double* cov, int32_t S, const 
     if (misaligned(mean, 8) || misaligned(cov, 8) || misaligned(matrix, 8) || misaligned(slot, 4))
         return refuse(BUSCA_SFRAME_EINVAL, "%s: misaligned pointer (8 bytes for float64, 4 for int32)", who);
     const KStore k{mean, cov, (const int*)slot, S, n};
-    SFRAME_LAUNCH(who, device, sframe_advance_kernel, dim3((unsigned)n), dim3(64), stream, k, matrix);
+    CAPI_LAUNCH(who, device, sframe_advance_kernel, dim3((unsigned)n), dim3(64), stream, k, matrix);
     return 0;
 }
 
@@ -114,7 +81,7 @@ extern "C" int busca_sframe_cost(const double* mean, const double* cov, int32_t 
     a.gated_cost = gated_cost, a.lambda = mc_lambda, a.rest = 1.0 - mc_lambda, a.max_distance = max_distance, a.limit = max_distance + 1e-5;
     a.max_iou = max_iou_distance, a.iou_limit = max_iou_distance + 1e-5;
     a.m = m, a.ld_cost = ld_cost, a.flags = flags, a.depth = depth;
-    SFRAME_LAUNCH(who, device, sframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, k, a);
+    CAPI_LAUNCH(who, device, sframe_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, k, a);
     return 0;
 }
 
@@ -147,6 +114,6 @@ extern "C" int busca_sframe_apply(double* mean, double* cov, int32_t S, const in
     f.free_slot = (const int*)free_slot, f.new_slot = (int*)new_slot, f.status = (int*)status;
     f.wa = (float)alpha, f.wb = (float)(1.0 - alpha);      // as busca_store_ema_fit forms them: the subtraction in float64, each rounded once
     f.m = m, f.E = E, f.n_free = n_free;
-    SFRAME_LAUNCH(who, device, sframe_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, k, f);
+    CAPI_LAUNCH(who, device, sframe_apply_kernel, dim3((unsigned)((long long)n + m)), dim3(64), stream, k, f);
     return 0;
 }

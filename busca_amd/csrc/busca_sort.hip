@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -26,51 +25,10 @@
 
 static_assert(SORT_MC == BUSCA_SORT_MC && SORT_CLAMP == BUSCA_SORT_CLAMP, "sort_kernel.hip.inc and busca_sort.h disagree on the flags");
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define SORT_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                      \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_SORT_EHIP, "%s: %s", who, hipGetErrorString(scope.err));       \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_SORT_EHIP, "%s: %s", who, hipGetErrorString(e_));                     \
-    } while (0)
-
-// the checks every call makes of the store and its slot list -> 0, or the refusal already recorded.  `cov_needed`: two calls read the means alone.
-static int store_args(const char* who, const double* mean, const double* cov, bool cov_needed, int32_t S, const int32_t* slot, int32_t n, int32_t device) {
-    if (S < 0 || n < 0) return refuse(BUSCA_SORT_EINVAL, "%s: negative size (S %d, n %d)", who, S, n);
-    if (device < 0) return refuse(BUSCA_SORT_EINVAL, "%s: negative device %d", who, device);
-    if (n == 0) return 0;
-    if (!mean || (cov_needed && !cov) || !slot) return refuse(BUSCA_SORT_EINVAL, "%s: null pointer (mean, cov and slot are required)", who);
-    if (misaligned(mean, 8) || misaligned(cov, 8) || misaligned(slot, 4))
-        return refuse(BUSCA_SORT_EINVAL, "%s: misaligned pointer (8 bytes for float64, 4 for int32)", who);
-    return 0;
-}
+#define CAPI_EHIP BUSCA_SORT_EHIP
+#define CAPI_EINVAL BUSCA_SORT_EINVAL
+#define CAPI_STORE_ARGS        // this library's calls take a Kalman store and its slot list
+#include "capi_prelude.hpp"
 
 // flags, clamp limit and grid of the two cost matrices -> 0, or the refusal already recorded
 static int cost_args(const char* who, int32_t n, int32_t m, int32_t flags, int known, double max_distance, dim3& grid) {
@@ -92,7 +50,7 @@ extern "C" int busca_sort_predict(double* mean, double* cov, int32_t S, const in
     const int rc = store_args(who, mean, cov, true, S, slot, n, device);
     if (rc != 0 || n == 0) return rc;
     const KStore k{mean, cov, (const int*)slot, S, n};
-    SORT_LAUNCH(who, device, sort_predict_kernel, dim3((unsigned)n), dim3(64), stream, k);
+    CAPI_LAUNCH(who, device, sort_predict_kernel, dim3((unsigned)n), dim3(64), stream, k);
     return 0;
 }
 
@@ -108,7 +66,7 @@ extern "C" int busca_sort_update(double* mean, double* cov, int32_t S, const int
     if (misaligned(meas, 8) || misaligned(conf, 8) || misaligned(det_index, 4) || misaligned(status, 4))
         return refuse(BUSCA_SORT_EINVAL, "%s: misaligned pointer (8 bytes for float64, 4 for int32)", who);
     const KStore k{mean, cov, (const int*)slot, S, n};
-    SORT_LAUNCH(who, device, sort_update_kernel, dim3((unsigned)n), dim3(64), stream, k, meas, (const int*)det_index, m, conf, (int*)status);
+    CAPI_LAUNCH(who, device, sort_update_kernel, dim3((unsigned)n), dim3(64), stream, k, meas, (const int*)det_index, m, conf, (int*)status);
     return 0;
 }
 
@@ -131,7 +89,7 @@ extern "C" int busca_sort_gate_cost(const double* mean, const double* cov, int32
     a.det_xyah = det_xyah, a.cost = cost, a.out = out, a.status = (int*)status;
     a.gated_cost = gated_cost, a.lambda = lambda, a.rest = 1.0 - lambda, a.max_distance = max_distance, a.limit = max_distance + 1e-5;
     a.m = m, a.ld_cost = ld_cost, a.flags = flags;
-    SORT_LAUNCH(who, device, sort_gate_cost_kernel, grid, dim3(256), stream, k, a);
+    CAPI_LAUNCH(who, device, sort_gate_cost_kernel, grid, dim3(256), stream, k, a);
     return 0;
 }
 
@@ -150,7 +108,7 @@ extern "C" int busca_sort_iou_cost(const double* mean, int32_t S, const int32_t*
     a.stale = stale, a.det_tlwh = det_tlwh, a.out = out;
     a.max_distance = max_distance, a.limit = max_distance + 1e-5;
     a.m = m, a.flags = flags;
-    SORT_LAUNCH(who, device, sort_iou_cost_kernel, grid, dim3(256), stream, k, a);
+    CAPI_LAUNCH(who, device, sort_iou_cost_kernel, grid, dim3(256), stream, k, a);
     return 0;
 }
 
@@ -161,6 +119,6 @@ extern "C" int busca_sort_camera_update(double* mean, int32_t S, const int32_t* 
     if (!matrix) return refuse(BUSCA_SORT_EINVAL, "%s: null pointer (matrix)", who);
     if (misaligned(matrix, 8)) return refuse(BUSCA_SORT_EINVAL, "%s: misaligned pointer (8 bytes for float64)", who);
     const KStore k{mean, nullptr, (const int*)slot, S, n};
-    SORT_LAUNCH(who, device, sort_camera_update_kernel, dim3((unsigned)((n + 255LL) / 256)), dim3(256), stream, k, matrix);
+    CAPI_LAUNCH(who, device, sort_camera_update_kernel, dim3((unsigned)((n + 255LL) / 256)), dim3(256), stream, k, matrix);
     return 0;
 }

@@ -3,7 +3,6 @@
 // store_kernel.hip.inc; nothing here is shared with the other two libraries.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -17,40 +16,8 @@
 
 #include "store_kernel.hip.inc"
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define STORE_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                     \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_STORE_EHIP, "%s: %s", who, hipGetErrorString(scope.err));      \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_STORE_EHIP, "%s: %s", who, hipGetErrorString(e_));                    \
-    } while (0)
+#define CAPI_EHIP BUSCA_STORE_EHIP
+#include "capi_prelude.hpp"
 
 // the sizes every call has: the slots S, the entries n of its list, the device -> 0, or the refusal already recorded
 static int size_args(const char* who, int32_t S, int32_t n, const char* n_name, int32_t device) {
@@ -85,7 +52,7 @@ extern "C" int busca_store_ring_add(float* gallery, int32_t* count, int32_t* new
     if (misaligned(gallery, 4) || misaligned(count, 4) || misaligned(newest, 4) || misaligned(slot, 4) || misaligned(feats, 4) || misaligned(det_index, 4))
         return refuse(BUSCA_STORE_EINVAL, "%s: misaligned pointer (4 bytes for float32 and int32)", who);
     const StoreRingArgs a{gallery, (int*)count, (int*)newest, mv_seen, (const int*)slot, feats, (const int*)det_index, is_new, S, budget, E, m};
-    STORE_LAUNCH(who, device, store_ring_add_kernel, dim3((unsigned)k), dim3(STORE_THREADS), stream, a);
+    CAPI_LAUNCH(who, device, store_ring_add_kernel, dim3((unsigned)k), dim3(STORE_THREADS), stream, a);
     return 0;
 }
 
@@ -95,8 +62,8 @@ extern "C" int busca_store_release(int32_t* count, uint8_t* mv_seen, int32_t S, 
     if (rc != 0 || k == 0) return rc;
     if (!count || !mv_seen || !slot) return refuse(BUSCA_STORE_EINVAL, "%s: null pointer (count, mv_seen and slot are required)", who);
     if (misaligned(count, 4) || misaligned(slot, 4)) return refuse(BUSCA_STORE_EINVAL, "%s: misaligned pointer (4 bytes for int32)", who);
-    STORE_LAUNCH(who, device, store_release_kernel, dim3((unsigned)((k + (long long)STORE_THREADS - 1) / STORE_THREADS)), dim3(STORE_THREADS), stream,
-                 (int*)count, mv_seen, S, (const int*)slot, k);
+    CAPI_LAUNCH(who, device, store_release_kernel, dim3((unsigned)((k + (long long)STORE_THREADS - 1) / STORE_THREADS)), dim3(STORE_THREADS), stream,
+                (int*)count, mv_seen, S, (const int*)slot, k);
     return 0;
 }
 
@@ -117,7 +84,7 @@ extern "C" int busca_store_mv_avg(const float* gallery, const int32_t* count, co
     // the weights as torch forms them from a Python scalar: the subtraction in float64, each value rounded once to float32
     const StoreMvAvgArgs a{gallery, (const int*)count, (const int*)newest, mv_avg, mv_seen, (const int*)slot, out, S, budget, E, num_active,
                            (float)a_act, (float)(1.0 - a_act), (float)a_inact, (float)(1.0 - a_inact)};
-    STORE_LAUNCH(who, device, store_mv_avg_kernel, dim3((unsigned)n), dim3(STORE_THREADS), stream, a);
+    CAPI_LAUNCH(who, device, store_mv_avg_kernel, dim3((unsigned)n), dim3(STORE_THREADS), stream, a);
     return 0;
 }
 
@@ -139,6 +106,6 @@ extern "C" int busca_store_ema_fit(float* gallery, int32_t S, int32_t ring, int3
         return refuse(BUSCA_STORE_EINVAL, "%s: misaligned pointer (4 bytes for float32 and int32)", who);
     const StoreEmaArgs a{gallery, feats, (const int*)group_slot, (const int*)group_old_row, (const int*)group_start, (const int*)src, S, ring, E, m,
                          k, (float)alpha, (float)(1.0 - alpha)};
-    STORE_LAUNCH(who, device, store_ema_fit_kernel, dim3((unsigned)g), dim3(STORE_THREADS), stream, a);
+    CAPI_LAUNCH(who, device, store_ema_fit_kernel, dim3((unsigned)g), dim3(STORE_THREADS), stream, a);
     return 0;
 }

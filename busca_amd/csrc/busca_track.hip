@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -26,51 +25,10 @@
 static_assert(KSTORE_FUSE_MOTION == BUSCA_TRACK_FUSE_MOTION && KSTORE_ONLY_POSITION == BUSCA_TRACK_ONLY_POSITION && KSTORE_GATE_ONLY == BUSCA_TRACK_GATE_ONLY,
               "kalman_store_kernel.hip.inc and busca_track.h disagree on the flags");
 
-static thread_local char g_err[320] = "";
-
-static int refuse(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
-// `device` current for one launch, the previous one back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceScope(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) err = hipSetDevice(device);
-        else if (err == hipSuccess) prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define TRACK_LAUNCH(who, device, kernel, grid, block, stream, ...)                                                     \
-    do {                                                                                                                \
-        DeviceScope scope(device);                                                                                      \
-        if (scope.err != hipSuccess) return refuse(BUSCA_TRACK_EHIP, "%s: %s", who, hipGetErrorString(scope.err));      \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)(stream), __VA_ARGS__);                                 \
-        const hipError_t e_ = hipGetLastError();                                                                        \
-        if (e_ != hipSuccess) return refuse(BUSCA_TRACK_EHIP, "%s: %s", who, hipGetErrorString(e_));                    \
-    } while (0)
-
-// the checks every call makes of the store and its slot list -> 0, or the refusal already recorded.  `cov_needed`: boxes reads the means alone.
-static int store_args(const char* who, const double* mean, const double* cov, bool cov_needed, int32_t S, const int32_t* slot, int32_t n, int32_t device) {
-    if (S < 0 || n < 0) return refuse(BUSCA_TRACK_EINVAL, "%s: negative size (S %d, n %d)", who, S, n);
-    if (device < 0) return refuse(BUSCA_TRACK_EINVAL, "%s: negative device %d", who, device);
-    if (n == 0) return 0;
-    if (!mean || (cov_needed && !cov) || !slot) return refuse(BUSCA_TRACK_EINVAL, "%s: null pointer (mean, cov and slot are required)", who);
-    if (misaligned(mean, 8) || misaligned(cov, 8) || misaligned(slot, 4))
-        return refuse(BUSCA_TRACK_EINVAL, "%s: misaligned pointer (8 bytes for float64, 4 for int32)", who);
-    return 0;
-}
+#define CAPI_EHIP BUSCA_TRACK_EHIP
+#define CAPI_EINVAL BUSCA_TRACK_EINVAL
+#define CAPI_STORE_ARGS        // this library's calls take a Kalman store and its slot list
+#include "capi_prelude.hpp"
 
 // the measurement operands of initiate / update
 static int meas_args(const char* who, int32_t n, const double* meas, const int32_t* det_index, int32_t m) {
@@ -93,7 +51,7 @@ extern "C" int busca_track_kalman_initiate(double* mean, double* cov, int32_t S,
     if (rc == 0) rc = meas_args(who, n, meas, det_index, m);
     if (rc != 0 || n == 0) return rc;
     const KStore k{mean, cov, (const int*)slot, S, n};
-    TRACK_LAUNCH(who, device, kstore_initiate_kernel, dim3((unsigned)n), dim3(64), stream, k, meas, (const int*)det_index, m);
+    CAPI_LAUNCH(who, device, kstore_initiate_kernel, dim3((unsigned)n), dim3(64), stream, k, meas, (const int*)det_index, m);
     return 0;
 }
 
@@ -103,7 +61,7 @@ extern "C" int busca_track_kalman_predict(double* mean, double* cov, int32_t S, 
     const int rc = store_args(who, mean, cov, true, S, slot, n, device);
     if (rc != 0 || n == 0) return rc;
     const KStore k{mean, cov, (const int*)slot, S, n};
-    TRACK_LAUNCH(who, device, kstore_predict_kernel, dim3((unsigned)n), dim3(64), stream, k, not_tracked);
+    CAPI_LAUNCH(who, device, kstore_predict_kernel, dim3((unsigned)n), dim3(64), stream, k, not_tracked);
     return 0;
 }
 
@@ -115,7 +73,7 @@ extern "C" int busca_track_kalman_update(double* mean, double* cov, int32_t S, c
     if (rc != 0 || n == 0) return rc;
     if (misaligned(status, 4)) return refuse(BUSCA_TRACK_EINVAL, "%s: misaligned pointer (4 bytes for int32)", who);
     const KStore k{mean, cov, (const int*)slot, S, n};
-    TRACK_LAUNCH(who, device, kstore_update_kernel, dim3((unsigned)n), dim3(64), stream, k, meas, (const int*)det_index, m, (int*)status);
+    CAPI_LAUNCH(who, device, kstore_update_kernel, dim3((unsigned)n), dim3(64), stream, k, meas, (const int*)det_index, m, (int*)status);
     return 0;
 }
 
@@ -129,7 +87,7 @@ extern "C" int busca_track_kalman_boxes(const double* mean, int32_t S, const int
     if (!out) return refuse(BUSCA_TRACK_EINVAL, "%s: null pointer (out)", who);
     if (misaligned(out, 8)) return refuse(BUSCA_TRACK_EINVAL, "%s: misaligned pointer (8 bytes for float64)", who);
     const KStore k{(double*)mean, nullptr, (const int*)slot, S, n};
-    TRACK_LAUNCH(who, device, kstore_boxes_kernel, dim3((unsigned)((n + 255LL) / 256)), dim3(256), stream, k, tlbr, out);
+    CAPI_LAUNCH(who, device, kstore_boxes_kernel, dim3((unsigned)((n + 255LL) / 256)), dim3(256), stream, k, tlbr, out);
     return 0;
 }
 
@@ -153,7 +111,7 @@ extern "C" int busca_track_round_cost(const double* mean, const double* cov, int
     const long long row_tiles = ((long long)n + PW_TA - 1) / PW_TA, col_tiles = ((long long)m + PW_TB - 1) / PW_TB;
     if (row_tiles > 65535) return refuse(BUSCA_TRACK_EINVAL, "%s: %d tracks need more workgroups than a grid holds (%d at most)", who, n, 65535 * PW_TA);
     const KStore k{(double*)mean, (double*)cov, (const int*)slot, S, n};
-    TRACK_LAUNCH(who, device, kstore_round_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, k, det_tlbr,
-                 motion ? det_xyah : nullptr, det_score, m, flags, lambda, out, (int*)status);
+    CAPI_LAUNCH(who, device, kstore_round_cost_kernel, dim3((unsigned)col_tiles, (unsigned)row_tiles), dim3(256), stream, k, det_tlbr,
+                motion ? det_xyah : nullptr, det_score, m, flags, lambda, out, (int*)status);
     return 0;
 }
